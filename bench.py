@@ -5,6 +5,7 @@
     python bench.py --gpus N --forget class                            ... class-wise forget (BASELINE configs[2])
     python bench.py --gpus N --scaling strong [--sync_bn 1]            ... the reference's global batch 256, 256/N per GPU
     python bench.py --gpus N --workload ddpm | sd                      CFG-DDPM class-forget | SD-v1 nsfw_removal (bf16)
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR   ... and the last timed step's outputs as DIR/*.npy
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...,
      or plain `python bench.py --gpus N`, which launches the N ranks itself)
 
@@ -112,6 +113,9 @@ def parse():
     ap.add_argument("--channels_last", type=int, default=0, help="1 = NHWC activations/weights")
     ap.add_argument("--fused_bn", type=int, default=1,
                     help="1 = BatchNorm(+residual)+ReLU as fused kernels (csrc/salun_norm.hip); 0 = PyTorch-ROCm ops")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="resnet18: after the timed steps, write what the last timed step left a caller as DIR/<name>.npy "
+                         "(see dump_outputs)")
     ap.add_argument("--salun_conv", type=int, default=1,
                     help="1 = convolutions on the hand-written fp32 MFMA kernels (csrc/salun_conv.hip); "
                          "0 = library (MIOpen) convolutions")
@@ -415,6 +419,35 @@ def selftest_workload(a):
         torch.distributed.destroy_process_group()
 
 
+DUMP_MOMENTUM_SAMPLE = 1 << 20  # momentum entries dumped (fixed seeded sample; the whole vector would exceed the budget)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, model, arena, opt, last):
+    """What the timed path handed its caller after its last step, as float32 / float64 .npy files:
+    params             the flat parameter vector after the last update (N18 float32; the model's weights)
+    bn_running_stats   every floating-point buffer of the model (BatchNorm running mean / var), concatenated
+    logits, loss       the last step's forward output (batch x 10) and its cross-entropy before any shard weight
+    momentum_sample    the SGD momentum buffer at DUMP_MOMENTUM_SAMPLE sorted indices drawn with default_rng(0)"""
+    arrays = {"params": arena.params.detach().float().cpu().numpy()}
+    bufs = [b.detach().reshape(-1).float() for _, b in model.named_buffers() if b.is_floating_point()]
+    arrays["bn_running_stats"] = torch.cat(bufs).cpu().numpy() if bufs else np.zeros(0, np.float32)
+    logits, loss = last
+    if logits is not None:
+        arrays["logits"] = logits.detach().float().cpu().numpy()
+        arrays["loss"] = np.array([float(loss.detach())], np.float64)
+    if opt.momentum_buffer is not None:
+        idx = np.sort(np.random.default_rng(0).choice(arena.n, min(DUMP_MOMENTUM_SAMPLE, arena.n), replace=False))
+        idx_dev = torch.from_numpy(idx).to(opt.momentum_buffer.device)
+        arrays["momentum_sample"] = opt.momentum_buffer[idx_dev].float().cpu().numpy()
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes over the {DUMP_MAX_BYTES} byte budget"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), v)
+    return {"dir": out_dir, "files": sorted(f"{k}.npy" for k in arrays), "bytes": total}
+
+
 def ensure_built():
     """A fresh clone has no libsalun.so: build it (hipcc cross-compiles) instead of dying with ImportError."""
     from unlearn_saliency_amd import _lib
@@ -431,6 +464,10 @@ def main():
         a.steps = {"resnet18": 177, "ddpm": 20, "sd": 3}[a.workload]
     if a.warmup is None:
         a.warmup = {"resnet18": 10, "ddpm": 3, "sd": 1}[a.workload]
+    if a.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if a.dump_outputs and a.workload != "resnet18":
+        raise SystemExit("--dump-outputs is implemented for the resnet18 workload only")
     if a.cpu_survey:
         a.cpu_steps, a.cpu_repeats = 20, 4
     if a.force_collectives:
@@ -516,6 +553,7 @@ def main():
     model.train()
     stream = iter(StepStream(forget_loader, retain_loader))
     seen = [0]  # samples THIS rank pushed through a step (ragged tail batches count for what they hold)
+    last = [None, None] if a.dump_outputs else None  # (logits, loss) of the latest step, kept for --dump-outputs
 
     def one_step(ev=None):
         x, y, w = next(stream)
@@ -524,8 +562,13 @@ def main():
             x = x.contiguous(memory_format=torch.channels_last)
         if x.size(0) == 0:  # strong scaling, tail batch smaller than the world: zero gradient from this rank
             opt.zero_grad()
+            if last is not None:
+                last[:] = [None, None]
         else:
-            loss = criterion(model(x), y)
+            logits = model(x)
+            loss = criterion(logits, y)
+            if last is not None:
+                last[:] = [logits, loss]
             if w != 1.0:  # data parallel, ragged tail batch: count-weighted shard mean
                 loss = loss * w
             opt.zero_grad()
@@ -582,6 +625,8 @@ def main():
         t = torch.tensor([samples], device=device, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.SUM)
         samples = float(t.item())
+    # before the calibration below, which launches the update again
+    dumped = dump_outputs(a.dump_outputs, model, arena, opt, last) if a.dump_outputs and rank == 0 else None
 
     # calibration, OUTSIDE the timed region (one rank, no collectives): what a HIP-event pair reads with nothing
     # between the two records, and the same update kernel launched back to back on the same vectors — the account of
@@ -644,7 +689,7 @@ def main():
             "collectives": bool(sdist.collectives_on()),
             "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": 1e3 * dt / a.steps, "higher_is_better": True, "scaling": a.scaling, "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
+            "dtype": "f32", "data": "synthetic", "dump_outputs": dumped,
             "config": {"workload": f"ResNet-18 (11,173,962 params) / CIFAR-10-shaped synthetic set, {what}, "
                                    "RL unlearning step with SalUn mask ratio 0.5, "
                                    "SGD lr 0.013 momentum 0.9 wd 5e-4, RandomCrop+flip on device",

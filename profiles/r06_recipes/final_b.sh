@@ -21,10 +21,9 @@ timeout 300 bash tools/pmc_multi.sh r06_conv_sq_b "SQ_VALU_MFMA_BUSY_CYCLES SQ_I
   echo "# shader clock under load (tools/clock_probe.py)";
   timeout 300 python tools/clock_probe.py 2>&1 | grep -v "amdgpu.ids\|Replacing\|random seed\|^45000" ) > gpurun_out/r06_corun.txt 2>&1
 ( for i in 1 2 3; do
-  for cfg in "plain|" "dp|--force_collectives" "dp_no_probe_4q|--force_collectives"; do
+  for cfg in "plain|" "dp|--force_collectives"; do
     name=${cfg%%|*}; extra=${cfg##*|}
-    envs=""; [ $name = dp_no_probe_4q ] && envs="GPU_MAX_HW_QUEUES=4 SALUN_STREAM_PROBE=0"
-    env $envs timeout 200 python bench.py --steps 60 --warmup 10 --no_cpu_baseline --no_ddpm --no_mask_gen --no_sd --no_dp $extra 2>/dev/null | grep '^{' | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('resnet18 $name', round(d['value'],2), 'steps/s', round(d['ms_per_step'],3), 'ms')"
+    timeout 200 python bench.py --steps 60 --warmup 10 --no_cpu_baseline --no_ddpm --no_mask_gen --no_sd --no_dp $extra 2>/dev/null | grep '^{' | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('resnet18 $name', round(d['value'],2), 'steps/s', round(d['ms_per_step'],3), 'ms')"
   done; done ) > gpurun_out/r06_dp_ws1.txt 2>&1
 cat gpurun_out/r06_dp_ws1.txt gpurun_out/r06_corun.txt
 python tools/pmc_traffic.py r06_n18:11173962 r06_nd:38632323 r06_ns:859520964 > gpurun_out/r06_pmc_traffic.json 2>/dev/null; head -c 600 gpurun_out/r06_pmc_traffic.json

@@ -22,7 +22,6 @@ done
 # data parallel at world size 1 (RCCL): with / without the target pass on a stream of its own (the tree's rule: without)
 export MASTER_PORT=29637
 one "dp                 " A=1 -- --force_collectives
-one "dp, 24 hw queues   " GPU_MAX_HW_QUEUES=24 -- --force_collectives
 one "plain              " A=1 --
 # diagnostics
 python tools/bench_sd.py --bf16 --steps 2 --warmup 1 --no_cpu_baseline --aten_origins 2>&1 >/dev/null | grep aten_origins | head -40

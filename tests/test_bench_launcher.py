@@ -10,6 +10,11 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+# the self-tests are host-side: ranks rendezvous over gloo even where a GPU is visible (RCCL would refuse two ranks on
+# one device)
+GLOO = {"OMP_NUM_THREADS": "1", "SALUN_DIST_BACKEND": "gloo"}
+
+
 def _run(args, extra_env=None, timeout=300):
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "LOCAL_WORLD_SIZE"):
@@ -20,7 +25,7 @@ def _run(args, extra_env=None, timeout=300):
 
 
 def test_gpus_2_selftest_creates_two_ranks_over_gloo():
-    r = _run(["--gpus", "2", "--selftest_launcher"], {"OMP_NUM_THREADS": "1"})
+    r = _run(["--gpus", "2", "--selftest_launcher"], GLOO)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -56,7 +61,7 @@ def test_class_forget_workload_shards_over_two_ranks():
     """BASELINE configs[2] under the launcher: `bench.py --gpus 2 --forget class` — both ranks mark the same 4,500
     samples of class 0 and their shards partition every global batch (gloo on the CPU; the device step itself is the
     single-GPU path of tests/test_classwise_gpu.py plus the all-reduce of tests/test_dist_gloo.py)."""
-    out = _json_line(_run(["--gpus", "2", "--forget", "class", "--selftest_workload"], {"OMP_NUM_THREADS": "1"}))
+    out = _json_line(_run(["--gpus", "2", "--forget", "class", "--selftest_workload"], GLOO))
     assert out["n_gpus"] == 2 and out["forget"] == "class" and out["forget_classes"] == [0]
     assert out["forget_samples"] == 4500 and out["retain_samples"] == 40500
     assert out["global_batch"] == 512 and out["forget_batches"] == 9     # weak scaling: 256 per rank
@@ -65,7 +70,7 @@ def test_class_forget_workload_shards_over_two_ranks():
 
 
 def test_strong_scaling_keeps_the_reference_global_batch():
-    out = _json_line(_run(["--gpus", "2", "--scaling", "strong", "--selftest_workload"], {"OMP_NUM_THREADS": "1"}))
+    out = _json_line(_run(["--gpus", "2", "--scaling", "strong", "--selftest_workload"], GLOO))
     assert out["forget"] == "random" and len(out["forget_classes"]) == 10
     assert out["global_batch"] == 256 and out["forget_batches"] == 18   # the reference's 18 forget batches per epoch
     assert out["shards_partition_every_batch"] and out["tail_batch"] == [74, 74]

@@ -29,7 +29,10 @@ def test_beta_schedules_and_tables(core):
         assert b.dtype == np.float64 and np.array_equal(b, core[f"betas_{s}"])
     a = (1 - t_(core["betas_linear"]).float()).cumprod(dim=0)
     assert np.array_equal(a.numpy(), core["alphas_cumprod"])
-    assert np.array_equal(a.sqrt().numpy(), core["sqrt_ab"])
+    # torch's float32 sqrt on the host is not correctly rounded, and its vector path differs between x86 hosts by one
+    # ulp (187 of the 1000 entries on an AMD EPYC host against the host that captured the table): at most one ulp
+    ulps = np.abs(a.sqrt().numpy().view(np.int32).astype(np.int64) - core["sqrt_ab"].view(np.int32).astype(np.int64))
+    assert ulps.max() <= 1, int(ulps.max())
 
 
 def test_qsample_bit_exact_vs_reference(oracle_mod, core):

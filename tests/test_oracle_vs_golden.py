@@ -129,7 +129,9 @@ def test_saliency_accumulation_tinycnn(oracle_mod, golden_dir):
         gflat = np.concatenate([p.grad.reshape(-1).numpy() for p in model.parameters()])
         oracle_mod.saliency_accumulate(acc, gflat, 1.0)
     assert [n_ for n_, _ in model.named_parameters()] == list(g["names"])
-    assert np.allclose(acc, g["acc"], rtol=1e-6, atol=1e-9)
+    # the gradients come from the host's torch convolution kernels, which differ between x86 hosts by a few float32 ulps
+    # of the largest entry (6e-8 absolute with entries up to 0.29 on an AMD EPYC host): absolute floor scaled to the vector
+    assert np.allclose(acc, g["acc"], rtol=1e-6, atol=1e-6 * float(np.abs(g["acc"]).max()))
     m = oracle_mod.mask_topk(acc, [oracle_mod.k_of(n, 0.5)])[0]
     assert np.array_equal(m, g["mask_05"])
 

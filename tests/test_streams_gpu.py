@@ -15,20 +15,38 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_side_streams_get_a_queue_of_their_own():
-    from unlearn_saliency_amd import streams
-    dev = torch.device("cuda", torch.cuda.current_device())
-    main = torch.cuda.current_stream(dev)
-    a = streams.concurrent_stream(dev)
-    b = streams.concurrent_stream(dev)
-    assert a.cuda_stream != b.cuda_stream and a.cuda_stream != main.cuda_stream
-    buf = torch.empty(32 * 1024 * 1024, dtype=torch.float32, device=dev).zero_()
-    flag = torch.zeros(1, dtype=torch.float32, device=dev)
-    assert streams._beside_main(main, a, buf, flag)
+_SIDE_STREAMS = """
+import torch
+from unlearn_saliency_amd import streams
+dev = torch.device("cuda", torch.cuda.current_device())
+main = torch.cuda.current_stream(dev)
+a = streams.concurrent_stream(dev)
+b = streams.concurrent_stream(dev)
+assert a.cuda_stream != b.cuda_stream and a.cuda_stream != main.cuda_stream
+buf = torch.empty(32 * 1024 * 1024, dtype=torch.float32, device=dev).zero_()
+flag = torch.zeros(1, dtype=torch.float32, device=dev)
+assert streams._beside_main(main, a, buf, flag)
+if streams.STATS.get("fallbacks", 0) == 0:
     assert streams._beside_main(main, b, buf, flag)
-    assert streams._beside_main(a, b, buf, flag)      # the second one was also probed against the first
-    # what the probe rejects: the stream itself is certainly not concurrent with itself
-    assert not streams._beside_main(a, a, buf, flag)
+    assert streams._beside_main(a, b, buf, flag)  # the second one was also probed against the first
+else:
+    # no candidate ran beside both (too few hardware queues for main + two side streams): the probe says so and
+    # hands out a stream that shares a queue — which the check must then see
+    assert not (streams._beside_main(main, b, buf, flag) and streams._beside_main(a, b, buf, flag))
+# what the probe rejects: the stream itself is certainly not concurrent with itself
+assert not streams._beside_main(a, a, buf, flag)
+print("side streams ok", streams.STATS)
+"""
+
+
+def test_side_streams_get_a_queue_of_their_own():
+    """In a fresh process, where a run hands its side streams out: in this one, the streams earlier tests and the
+    libraries they loaded created have already decided which hardware queues new streams land on.  The first side stream
+    always gets a queue of its own; a second one does only where the runtime provides enough queues, and where it does
+    not, the probe must report the fallback (STATS) instead of claiming a queue it did not find."""
+    r = subprocess.run([sys.executable, "-c", _SIDE_STREAMS], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0 and "side streams ok" in r.stdout, r.stderr[-3000:]
+    print(r.stdout)
 
 
 def _line(extra, port):

@@ -1,11 +1,11 @@
 """Side streams that really run beside the main stream.
 
-HIP maps every stream onto one of a few hardware queues (GPU_MAX_HW_QUEUES, 4 by default); two streams on the same
+HIP maps every stream onto one of a few hardware queues (4 by default); two streams on the same
 queue execute strictly one after the other.  Single-process runs got lucky — the current stream and the first
 `torch.cuda.Stream()` landed on different queues — but with a process group the RCCL communicator's own streams shift
 the assignment, and the backward-weight side stream of resblock.py ended up on the MAIN stream's queue: the
 data-parallel ResNet-18 step ran every kernel back to back, 10.03 ms instead of 8.53 (round 6,
-`bench.py --force_collectives`; with GPU_MAX_HW_QUEUES=8 the same run takes 8.66 ms).
+`bench.py --force_collectives`; with eight hardware queues the same run took 8.66 ms).
 
 `concurrent_stream(device)` therefore PROBES: it keeps the first of a few candidate streams on which a small kernel
 finishes while a few milliseconds of work are still queued on the current stream — and, when a process group over
@@ -13,7 +13,7 @@ RCCL exists, beside which a small all-reduce completes while the candidate is bu
 pair up across ranks, so they are issued only from `prepare()`, which `dist.init_from_env` calls on every rank right after
 it created the process group (every rank probes the SAME number of candidates whatever each finds) and which stocks a
 small pool; `concurrent_stream()` hands out the pool first and otherwise probes WITHOUT collectives — a rank that skips a
-backward pass (empty shard) must not leave the others waiting in one.  ~10 - 40 ms per stream, once.
+backward pass (empty shard) must not leave the others waiting in one.  ~10 - 100 ms per stream, once.
 """
 from __future__ import annotations
 
@@ -30,10 +30,18 @@ _accepted: dict = {}  # device -> side streams handed out so far: a new one must
                       # data-parallel DDPM step 19 % — 126 vs 106 ms — although the two are busy in different phases)
 
 
-def _busy(stream, buf, n=24):
-    with torch.cuda.stream(stream):
-        for _ in range(n):          # ~3 ms of streaming passes over 128 MB
-            buf.mul_(1.0)
+_BUSY_SPINS = 1200  # s_sleep(127) rounds of the one-wave clock probe: ~3.4 us each at 2.4 GHz, ~4 ms in all
+
+
+def _busy(stream, buf):
+    """Occupy `stream` for ~4 ms with ONE launch (salun_clock_probe, a single wave that sleeps; its 16-byte output goes
+    to the head of `buf`).  A train of short kernels left the verdict to the host: when enqueueing them took about as
+    long as running them, a candidate on a queue of its own finished too late to count as beside."""
+    import ctypes
+    from . import _lib
+    out = buf[:4].view(torch.int64)
+    _lib.check(_lib.lib().salun_clock_probe(ctypes.c_void_p(out.data_ptr()), 1, _BUSY_SPINS,
+                                            ctypes.c_void_p(stream.cuda_stream)), "salun_clock_probe")
 
 
 def _beside_main(main, cand, buf, flag) -> bool:

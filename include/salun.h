@@ -639,6 +639,41 @@ int salun_dropout(const float *x /*dev*/, float *y /*dev*/, int64_t n_samples, i
 /* *value += inc on the stream (advances a device-resident seed between graph replays). */
 int salun_u64_add(uint64_t *value /*dev*/, uint64_t inc, salun_stream_t stream);
 
+/* ----------------------------------------------------------------- K17 --
+ * IU / WoodFisher baseline (Classification/unlearn/Wfisher.py:47-198) from two scalars per retain sample,
+ * a_i = <g_0, g_i> and b_i = <v, g_i>, computed from one batched eval-mode backward per batch
+ * without materialising any per-sample gradient.  `out` (dev, B x 2 fp64, row-major: [i][0] for tangent 0 = g_0,
+ * [i][1] for tangent 1 = v) is ACCUMULATED into, so one buffer collects every layer of a network.  All reductions
+ * are fp64, per-workgroup partials in `ws` then a fixed-order finish: bit-identical from run to run, no atomics.
+ * Workspace of the conv / BN dots: salun_iu_dot_workspace_bytes(B, n) with n = the per-sample element count.
+ *
+ * conv:    y2 (B, 2K, P, Q) = conv(x, [U_0; U_1]) (+ [u_b0; u_b1]);  dy (B, K, P, Q);  n = K*P*Q
+ *          out[i][j] += sum_{c<n} y2[i][j*n + c] * dy[i][c]
+ * BN eval: x, dy (B, C, HW);  out[i][j] += sum_{c,pq} dy * (ug_j[c] * (x - mean[c]) / sqrt(var[c] + eps) + ub_j[c])
+ * linear:  x (B, K), dy (B, M), U_j (M, K), u_bj (M) or both NULL;  out[i][j] += sum_m dy[i][m] (U_j x_i + u_bj)[m]
+ * B <= 65535 for the conv / BN dots. */
+size_t salun_iu_dot_workspace_bytes(int B, int64_t n);
+int salun_iu_conv_dot(const float *y2 /*dev*/, const float *dy /*dev*/, int B, int64_t n, double *out /*dev, B*2*/,
+                      void *ws /*dev*/, size_t ws_bytes, salun_stream_t stream);
+int salun_iu_bn_dot(const float *x /*dev*/, const float *dy /*dev*/, const float *running_mean /*dev, C*/,
+                    const float *running_var /*dev, C*/, double eps, const float *u0_gamma /*dev, C*/,
+                    const float *u0_beta /*dev, C*/, const float *u1_gamma /*dev, C*/, const float *u1_beta /*dev, C*/,
+                    int B, int C, int HW, double *out /*dev, B*2*/, void *ws /*dev*/, size_t ws_bytes,
+                    salun_stream_t stream);
+int salun_iu_linear_dot(const float *x /*dev*/, const float *dy /*dev*/, const float *u0_w /*dev*/,
+                        const float *u0_b /*dev or NULL*/, const float *u1_w /*dev*/, const float *u1_b /*dev or NULL*/,
+                        int B, int M, int K, double *out /*dev, B*2*/, salun_stream_t stream);
+/* The WoodFisher loop in scalar form, one thread in fp64:  s = 1, beta = 0;  for i < n (ab = (a_i, b_i) pairs of
+ * samples 1 .. n of the reference's walk):  t = s a_i;  beta += (b_i - beta a_i) s / (N + t);  s *= N / (N + t).
+ * out (dev, 2 fp64) = {beta, s}: the reference's k = v - beta g_0 and o = s g_0.  No host synchronisation. */
+int salun_iu_recurrence(const double *ab /*dev, n*2*/, int64_t n, double N, double *out /*dev, 2*/,
+                        salun_stream_t stream);
+/* p[e] <- (float)((double)p[e] + alpha * ((double)v[e] - beta * (double)g0[e]))  where mask[e] != 0, everywhere
+ * when mask is NULL; masked-out weights are not written.  beta: dev, 1 fp64 (salun_iu_recurrence's out[0]).
+ * 16 B / element, 17 with a mask. */
+int salun_iu_apply(float *p /*dev*/, const float *v /*dev*/, const float *g0 /*dev*/, const double *beta /*dev*/,
+                   const uint8_t *mask /*dev or NULL*/, double alpha, int64_t n, salun_stream_t stream);
+
 /* Counter-based generators shared bit-for-bit with oracle/ (splitmix64 of
  * seed + index; integer arithmetic only, so CPU and GPU agree exactly):
  *   uniform: lo + (hi-lo) * (top 24 bits / 2^24);

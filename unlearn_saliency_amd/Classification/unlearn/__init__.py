@@ -5,8 +5,9 @@
 in place; unknown names raise NotImplementedError exactly like the reference.  All 17
 registry names are kept so command lines stay drop-in; the SalUn hot path (RL with a
 mask), the baselines that share its fused step (GA, GA_l1, FT, FT_l1, raw, boundary_shrink,
-boundary_expanding — SURVEY.md §8 F1) and the proximal variant (RL_proximal, F2) are
-implemented; the Fisher / pruning / retrain baselines are registered but raise with a scope note.
+boundary_expanding — SURVEY.md §8 F1), the proximal variant (RL_proximal, F2) and the IU / WoodFisher
+baseline (wfisher: per-sample gradient dots from one batched backward) are implemented; the
+Fisher / pruning / retrain baselines are registered but raise with a scope note.
 """
 from .boundary_ex import boundary_expanding
 from .boundary_sh import boundary_shrink
@@ -15,6 +16,7 @@ from .GA import GA, GA_l1
 from .impl import (FusedMaskedSGD, iterative_unlearn, load_unlearn_checkpoint, save_unlearn_checkpoint)
 from .RL import RL
 from .RL_pro import RL_proximal
+from .Wfisher import Wfisher
 
 
 def raw(data_loaders, model, criterion, args, mask=None):
@@ -35,7 +37,7 @@ _REGISTRY = {
     "retrain": _out_of_scope("retrain", "re-training from scratch is pre-training, not unlearning arithmetic"),
     "fisher": _out_of_scope("fisher", "Fisher-forgetting baseline"),
     "fisher_new": _out_of_scope("fisher_new", "Fisher-forgetting baseline"),
-    "wfisher": _out_of_scope("wfisher", "influence-unlearning baseline"),
+    "wfisher": Wfisher,
     "FT_prune": _out_of_scope("FT_prune", "pruning baseline"),
     "FT_prune_bi": _out_of_scope("FT_prune_bi", "pruning baseline"),
     "GA_prune": _out_of_scope("GA_prune", "pruning baseline"),

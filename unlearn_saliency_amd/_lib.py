@@ -158,6 +158,13 @@ SIGNATURES = {
     "salun_gemm_bf16_tn": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "salun_dropout": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_double, c_uint64, c_void_p, c_void_p]),
     "salun_u64_add": (c_int, [c_void_p, c_uint64, c_void_p]),
+    "salun_iu_dot_workspace_bytes": (c_size_t, [c_int, c_int64]),
+    "salun_iu_conv_dot": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "salun_iu_bn_dot": (c_int, [c_void_p] * 4 + [c_double] + [c_void_p] * 4 + [c_int] * 3 + [c_void_p, c_void_p,
+                                                                                           c_size_t, c_void_p]),
+    "salun_iu_linear_dot": (c_int, [c_void_p] * 6 + [c_int] * 3 + [c_void_p, c_void_p]),
+    "salun_iu_recurrence": (c_int, [c_void_p, c_int64, c_double, c_void_p, c_void_p]),
+    "salun_iu_apply": (c_int, [c_void_p] * 5 + [c_double, c_int64, c_void_p]),
     "salun_fill_uniform": (c_int, [c_void_p, c_int64, c_uint64, c_double, c_double, c_void_p]),
     "salun_fill_normal": (c_int, [c_void_p, c_int64, c_uint64, c_double, c_double, c_void_p]),
     "salun_fill_u8": (c_int, [c_void_p, c_int64, c_uint64, c_void_p]),

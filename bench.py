@@ -6,6 +6,7 @@
     python bench.py --gpus N --scaling strong [--sync_bn 1]            ... the reference's global batch 256, 256/N per GPU
     python bench.py --gpus N --workload ddpm | sd                      CFG-DDPM class-forget | SD-v1 nsfw_removal (bf16)
     python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR   ... and the last timed step's outputs as DIR/*.npy
+    python bench.py --gpus 1 --full                                    ... and every secondary figure (see below)
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...,
      or plain `python bench.py --gpus N`, which launches the N ranks itself)
 
@@ -23,10 +24,19 @@ Nothing is skipped inside the timed region; inputs are resident in HBM before it
 `value`: weak scaling (default) = (steps x ranks) / seconds — every rank processes its own 256-sample batch per step;
 strong scaling = steps / seconds — one step is one reference step (global batch 256) whatever the rank count.
 `samples_per_sec` counts the samples actually processed (ragged tail batches count for what they hold).
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, makes the SalUn mask, warms up,
+times the steps, writes --dump-outputs and prints the line; what it reports beside the headline comes from the timed
+steps' own HIP events:
   roofline      the hand-written kernel that owns the optimizer tail, salun_masked_sgd_step: algorithmic
                 bytes (21 B x N) / mean launch duration (HIP events on the launch stream, inside the timed steps)
+  fwd_bwd       forward + backward device time per step against the fp32 MFMA peak
+`--full` adds what takes runs of its own (minutes, most of them on the host): the timed mask generation (`mask_gen`),
+the event-pair calibration of `roofline`, and with one rank
   cpu_baseline  the un-fused reference op sequence (oracle/torch_ref.py) timed on this host's cores, bounded sample
+  ddpm, sd      the diffusion workloads' lines (short windows; sd in a subprocess)
+  dp_ws1        every workload again through the data-parallel path at world size 1 (subprocesses)
+The --no_* options below leave single parts out of a --full run.  `--workload ddpm | sd` time their CPU reference step
+with --full only.
 """
 from __future__ import annotations
 
@@ -50,7 +60,7 @@ FWD_BWD_GFLOP_PER_IMG = 3.329  # SURVEY.md §6 (FlopCounterMode on the reference
 SGD_BYTES_PER_ELEM = 21      # r p,g,buf (12) + r mask (1) + w p,buf (8)
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None,
@@ -85,25 +95,30 @@ def parse():
                     help="host-only check of the benchmark's data side under the launcher: the N ranks' shards of the "
                          "(random / class-wise) forget set partition every global batch; no device work")
     ap.add_argument("--batch_size", type=int, default=256, help="per-GPU batch (reference: 256)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: timed mask generation, event calibration, "
+                         "CPU baselines, the DDPM / SD blocks and the dp_ws1 figures (minutes; off by default)")
     ap.add_argument("--no_cpu_baseline", action="store_true")
     ap.add_argument("--cpu_steps", type=int, default=12,
-                    help="reference-sequence steps timed on the host CPU, in --cpu_repeats groups (SURVEY.md D3 asks 20 = "
-                         "--cpu_survey: 12 keep the default run, which also carries the DDPM block and its one CPU "
-                         "step, near three minutes; the spread over the groups is reported)")
+                    help="reference-sequence steps timed on the host CPU by --full, in --cpu_repeats groups (SURVEY.md "
+                         "D3 asks 20 = --cpu_survey: 12 keep the --full run, which also carries the DDPM block and its "
+                         "one CPU step, near three minutes; the spread over the groups is reported)")
     ap.add_argument("--cpu_repeats", type=int, default=4)
     ap.add_argument("--cpu_survey", action="store_true",
                     help="the CPU baseline at the sample sizes SURVEY.md D3 asks for: 20 RL steps (4 groups of 5, ~2 min "
                          "on 128 threads) instead of the default 12")
-    ap.add_argument("--no_mask_gen", action="store_true", help="skip timing Phase A (a random mask is used)")
+    ap.add_argument("--no_mask_gen", action="store_true",
+                    help="skip Phase A (a random mask is used instead of the saliency mask)")
     ap.add_argument("--no_ddpm", action="store_true",
-                    help="skip the CFG-DDPM class-forget block the default one-GPU line carries beside the ResNet-18 "
+                    help="skip the CFG-DDPM class-forget block the --full one-GPU line carries beside the ResNet-18 "
                          "figures (north_star's second target; `--workload ddpm` is the full-length form)")
     ap.add_argument("--no_sd", action="store_true",
-                    help="skip the SD-v1 U-Net block (BASELINE configs[4], bf16, batch 8) of the default one-GPU line")
+                    help="skip the SD-v1 U-Net block (BASELINE configs[4], bf16, batch 8) of the --full one-GPU line")
     ap.add_argument("--sd_steps", type=int, default=4)
     ap.add_argument("--no_dp", action="store_true",
-                    help="skip the `dp_ws1` figures: the same steps through the data-parallel path (process group over "
-                         "RCCL at world size 1, gradient slices all-reduced behind backward), each in a subprocess")
+                    help="skip the `dp_ws1` figures of --full: the same steps through the data-parallel path (process "
+                         "group over RCCL at world size 1, gradient slices all-reduced behind backward), each in a "
+                         "subprocess")
     ap.add_argument("--ddpm_steps", type=int, default=10)
     ap.add_argument("--ddpm_mask_batches", type=int, default=8,
                     help="forget batches of the embedded DDPM Phase A (the reference's 40 scale linearly)")
@@ -119,7 +134,7 @@ def parse():
     ap.add_argument("--salun_conv", type=int, default=1,
                     help="1 = convolutions on the hand-written fp32 MFMA kernels (csrc/salun_conv.hip); "
                          "0 = library (MIOpen) convolutions")
-    return ap.parse_args()
+    return ap.parse_args(argv)
 
 
 class StepStream:
@@ -170,9 +185,12 @@ def build_workload(device, rank, world, per_gpu_bs, forget_mode="random", class_
     return model, mk(forget), mk(retain)
 
 
-def time_mask_gen(model, forget_loader, criterion):
+def time_mask_gen(model, forget_loader, criterion, full=True):
     """Phase A wall time on this GPU: 4,500 forget samples fwd/bwd + flat accumulation + all 10 thresholds
-    (u8 masks resident in HBM).  File writing (10 x 89 MB int64 .pt) is reported separately by generate_mask.py."""
+    (u8 masks resident in HBM).  File writing (10 x 89 MB int64 .pt) is reported separately by generate_mask.py.
+    Returns (ratio-0.5 mask, figures).  `full=False` makes the mask alone and returns no figures: the same two passes over
+    the forget loader all the same, since each pass draws its shuffle and crops from the generators the timed steps'
+    batches come from next."""
     from unlearn_saliency_amd.Classification.generate_mask import (THRESHOLD_LIST, accumulate_saliency,
                                                                   masks_from_saliency)
     from unlearn_saliency_amd import ops
@@ -187,6 +205,8 @@ def time_mask_gen(model, forget_loader, criterion):
         masks = masks_from_saliency(acc, THRESHOLD_LIST)
         torch.cuda.synchronize()
         t2 = time.perf_counter()
+    if not full:
+        return masks[0.5].clone(), None
     first_call, saliency_sec = t2 - t1, t1 - t0
     # the same call again with the ten outputs handed back to the caching allocator first: what the select costs the
     # host once the 112 MB of masks no longer come from a fresh hipMalloc (the pass above allocates them behind a
@@ -302,8 +322,7 @@ def dp_ws1_line(extra, plain_ms):
     """One workload through the data-parallel path at world size 1 in a subprocess (a process group cannot be created
     and torn down inside the timed process without disturbing it): the fields that matter of its bench line."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--force_collectives", "--no_cpu_baseline",
-           "--no_ddpm", "--no_sd", "--no_dp"] + extra
+    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--force_collectives"] + extra  # a plain run
     env = dict(os.environ)
     env.setdefault("MASTER_PORT", "29621")
     t0 = time.perf_counter()
@@ -343,10 +362,10 @@ def dp_ws1_checked(extra, plain_ms):
 
 
 def sd_block(a):
-    """`bench.py --workload sd --gpus 1` (bf16, batch 8) in a subprocess; its line's fields that matter."""
+    """`bench.py --workload sd --gpus 1 --full` (bf16, batch 8) in a subprocess; its line's fields that matter."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--workload", "sd", "--steps", str(a.sd_steps),
-           "--warmup", "1"] + (["--no_cpu_baseline"] if a.no_cpu_baseline else [])
+           "--warmup", "1", "--full"] + (["--no_cpu_baseline"] if a.no_cpu_baseline else [])
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -496,7 +515,7 @@ def main():
         # RANK / WORLD_SIZE through dist.init_from_env and shard their batches (BASELINE configs[3] / [4])
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         argv = ["--gpus", str(a.gpus), "--steps", str(a.steps), "--warmup", str(a.warmup),
-                "--scaling", a.scaling] + (["--no_cpu_baseline"] if a.no_cpu_baseline else []) \
+                "--scaling", a.scaling] + (["--no_cpu_baseline"] if a.no_cpu_baseline or not a.full else []) \
             + (["--digest"] if a.digest else [])
         if a.workload == "ddpm":
             import bench_ddpm
@@ -545,7 +564,7 @@ def main():
         mask_u8 = ops.mask_topk(ops.fill_normal(N18, 5, 0.0, 1e-3), [int(N18 * 0.5)])[0]
     else:
         with contextlib.redirect_stdout(sys.stderr):
-            mask_u8, mask_gen = time_mask_gen(model, forget_loader, criterion)
+            mask_u8, mask_gen = time_mask_gen(model, forget_loader, criterion, full=a.full)
     assert ops.mask_popcount(mask_u8) == int(N18 * 0.5)
 
     opt = FusedMaskedSGD(arena, 0.013, momentum=0.9, weight_decay=5e-4)
@@ -628,11 +647,11 @@ def main():
     # before the calibration below, which launches the update again
     dumped = dump_outputs(a.dump_outputs, model, arena, opt, last) if a.dump_outputs and rank == 0 else None
 
-    # calibration, OUTSIDE the timed region (one rank, no collectives): what a HIP-event pair reads with nothing
+    # --full: calibration, OUTSIDE the timed region (one rank, no collectives): what a HIP-event pair reads with nothing
     # between the two records, and the same update kernel launched back to back on the same vectors — the account of
     # how much of the in-step figure is the kernel and how much the two markers around it
     ev_overhead_us = iso_us = None
-    if world == 1 and not sdist.collectives_on():
+    if a.full and world == 1 and not sdist.collectives_on():
         cal = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(40)]
         for s_, e_ in cal[:20]:
             s_.record()
@@ -719,7 +738,7 @@ def main():
                                    "first event is recorded after backward's side-stream join, so the pair holds the "
                                    "kernel and the two markers); `event_pair_overhead_us` = an empty pair, "
                                    "`back_to_back_launch_us` = the same launch repeated with warm caches, both taken "
-                                   "after the timed region"},
+                                   "after the timed region by --full runs only"},
             "fwd_bwd": {"bound": "mfma", "gflop_per_step": flop_per_step_rank,
                         "achieved": flop_per_step_rank / (fb_mean_s * 1e3) if fb_mean_s else None,
                         "peak": FP32_MATRIX_PEAK_TF, "unit": "TFLOP/s",
@@ -732,10 +751,10 @@ def main():
                                    else "BN/ReLU/pool/fc: PyTorch-ROCm")) if n_salun_convs else
                                 "convolutions/GEMMs run in MIOpen/rocBLAS fp32 through PyTorch-ROCm"},
         }
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             with contextlib.redirect_stdout(sys.stderr):
                 out["cpu_baseline"] = cpu_baseline(a.batch_size, a.cpu_steps, a.cpu_repeats)
-        if (world == 1 and not a.no_ddpm and a.forget == "random" and a.scaling == "weak"
+        if (a.full and world == 1 and not a.no_ddpm and a.forget == "random" and a.scaling == "weak"
                 and not sdist.collectives_on()):
             # north_star's second target beside the headline: CFG-DDPM class-forget (BASELINE configs[3]) — the same
             # step `--workload ddpm` times, a shorter window, one reference step on the CPU (~80 s on 128 threads)

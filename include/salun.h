@@ -674,6 +674,41 @@ int salun_iu_recurrence(const double *ab /*dev, n*2*/, int64_t n, double N, doub
 int salun_iu_apply(float *p /*dev*/, const float *v /*dev*/, const float *g0 /*dev*/, const double *beta /*dev*/,
                    const uint8_t *mask /*dev or NULL*/, double alpha, int64_t n, salun_stream_t stream);
 
+/* ----------------------------------------------------------------- K18 --
+ * Fisher forgetting (`fisher_new`, Classification/unlearn/fisher.py:50-114).  The reference runs one
+ * backward per class y and adds mean_i(prob[:, y]) * grad_y^2; in eval mode grad_y is linear in each layer's output
+ * gradient, so all G class tangents come from one backward as a grouped dy [G*B, ...] over a shared input x [B, ...],
+ * and F (dev fp32, ACCUMULATED into) gets sum_g w[g] * s_g^2 with s_g the complete group-g gradient.  Every group sum
+ * is reduced to completion in a fixed order before it is squared; no float atomics: bit-identical from run to run.
+ *
+ * conv:   x (B, C, H, W), dy (G*B, K, P, Q), w (G), F (K, C, R, R): s_g = conv2d_backward_weight(x, dy_g) on the
+ *         package's kernels (the shapes salun_conv2d_backward_weight takes; SALUN_EINVAL outside them).
+ *         Workspace: salun_ff_conv_sq_workspace_bytes (0 = outside the domain).
+ * linear: x (B, K), dy (G*B, M), F (M, K): s_g[m, k] = sum_{i<B} dy[g*B+i, m] x[i, k].
+ * vector: dy (G*B, C, HW); F_beta[c] += sum_g w_g (sum_{i,pq} dy)^2 (conv / Linear bias, BN beta) and, when F_gamma is
+ *         given, F_gamma[c] += sum_g w_g (sum dy (x - mean[c]) / sqrt(var[c] + eps))^2 with x (B, C, HW) (BN gamma).
+ *         Workspace: salun_ff_vec_sq_workspace_bytes(G, C). */
+size_t salun_ff_conv_sq_workspace_bytes(int G, int B, int C, int K, int R, int P, int Q);
+int salun_ff_conv_sq(const float *x /*dev*/, const float *dy /*dev*/, const float *w /*dev, G*/, float *F /*dev*/,
+                     int G, int B, int C, int H, int W, int K, int R, int stride, int pad, int P, int Q,
+                     void *ws /*dev*/, size_t ws_bytes, salun_stream_t stream);
+int salun_ff_linear_sq(const float *x /*dev*/, const float *dy /*dev*/, const float *w /*dev, G*/, float *F /*dev*/,
+                       int G, int B, int M, int K, salun_stream_t stream);
+size_t salun_ff_vec_sq_workspace_bytes(int G, int C);
+int salun_ff_vec_sq(const float *x /*dev or NULL*/, const float *dy /*dev*/, const float *running_mean /*dev or NULL*/,
+                    const float *running_var /*dev or NULL*/, double eps, const float *w /*dev, G*/, int G, int B,
+                    int C, int HW, float *F_gamma /*dev or NULL*/, float *F_beta /*dev or NULL*/, void *ws /*dev*/,
+                    size_t ws_bytes, salun_stream_t stream);
+/* The reference's get_mean_var + p = mu + sqrt(var) z over the flat parameter arena, in place.  table (dev int64,
+ * nparam rows of 7): offset, shape[0], shape[1] (1 for 1-D), prod(shape[2:]) (<= 256), flags (1: shape[0] ==
+ * num_classes, 2: ndim > 1), the class row to override (-1: none), the parameter's first tile (a tile is one dim-0
+ * row of a multi-dimensional parameter or 256 elements of a 1-D one; ntiles in all).  F is the raw sum of the batches'
+ * grad2 terms: var = alpha * min(1 / (F / nbatches + 1e-8), 1e3 [, 1e2]); mean over dim 1 when ndim > 1; override row:
+ * mu = 0, var = 1e-4; x10 when shape[0] == num_classes or ndim == 1.  z[e] is salun_fill_normal(seed, 0, 1)'s value at
+ * the flat index e. */
+int salun_ff_apply(float *p /*dev*/, const float *F /*dev*/, const int64_t *table /*dev*/, int nparam, int64_t ntiles,
+                   double nbatches, double alpha, uint64_t seed, salun_stream_t stream);
+
 /* Counter-based generators shared bit-for-bit with oracle/ (splitmix64 of
  * seed + index; integer arithmetic only, so CPU and GPU agree exactly):
  *   uniform: lo + (hi-lo) * (top 24 bits / 2^24);

@@ -6,11 +6,14 @@ in place; unknown names raise NotImplementedError exactly like the reference.  A
 registry names are kept so command lines stay drop-in; the SalUn hot path (RL with a
 mask), the baselines that share its fused step (GA, GA_l1, FT, FT_l1, raw, boundary_shrink,
 boundary_expanding — SURVEY.md §8 F1), the proximal variant (RL_proximal, F2) and the IU / WoodFisher
-baseline (wfisher: per-sample gradient dots from one batched backward) are implemented; the
-Fisher / pruning / retrain baselines are registered but raise with a scope note.
+baseline (wfisher: per-sample gradient dots from one batched backward) and Fisher forgetting
+(fisher_new: all classes' squared batch gradients from one pass over the activations) are
+implemented; the per-sample empirical Fisher (fisher), pruning and retrain baselines are registered but raise with a
+scope note.
 """
 from .boundary_ex import boundary_expanding
 from .boundary_sh import boundary_shrink
+from .fisher import fisher_new
 from .FT import FT, FT_l1
 from .GA import GA, GA_l1
 from .impl import (FusedMaskedSGD, iterative_unlearn, load_unlearn_checkpoint, save_unlearn_checkpoint)
@@ -36,7 +39,7 @@ _REGISTRY = {
     "raw": raw, "RL": RL, "GA": GA, "FT": FT, "FT_l1": FT_l1, "GA_l1": GA_l1,
     "retrain": _out_of_scope("retrain", "re-training from scratch is pre-training, not unlearning arithmetic"),
     "fisher": _out_of_scope("fisher", "Fisher-forgetting baseline"),
-    "fisher_new": _out_of_scope("fisher_new", "Fisher-forgetting baseline"),
+    "fisher_new": fisher_new,
     "wfisher": Wfisher,
     "FT_prune": _out_of_scope("FT_prune", "pruning baseline"),
     "FT_prune_bi": _out_of_scope("FT_prune_bi", "pruning baseline"),

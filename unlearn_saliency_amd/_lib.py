@@ -165,6 +165,13 @@ SIGNATURES = {
     "salun_iu_linear_dot": (c_int, [c_void_p] * 6 + [c_int] * 3 + [c_void_p, c_void_p]),
     "salun_iu_recurrence": (c_int, [c_void_p, c_int64, c_double, c_void_p, c_void_p]),
     "salun_iu_apply": (c_int, [c_void_p] * 5 + [c_double, c_int64, c_void_p]),
+    "salun_ff_conv_sq_workspace_bytes": (c_size_t, [c_int] * 7),
+    "salun_ff_conv_sq": (c_int, [c_void_p] * 4 + [c_int] * 11 + [c_void_p, c_size_t, c_void_p]),
+    "salun_ff_linear_sq": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p]),
+    "salun_ff_vec_sq_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "salun_ff_vec_sq": (c_int, [c_void_p] * 4 + [c_double, c_void_p] + [c_int] * 4 + [c_void_p] * 3
+                        + [c_size_t, c_void_p]),
+    "salun_ff_apply": (c_int, [c_void_p] * 3 + [c_int, c_int64, c_double, c_double, c_uint64, c_void_p]),
     "salun_fill_uniform": (c_int, [c_void_p, c_int64, c_uint64, c_double, c_double, c_void_p]),
     "salun_fill_normal": (c_int, [c_void_p, c_int64, c_uint64, c_double, c_double, c_void_p]),
     "salun_fill_u8": (c_int, [c_void_p, c_int64, c_uint64, c_void_p]),

@@ -16,8 +16,8 @@ for i in 1 2; do
   one "pack per model     " SALUN_BF16_BATCH_PACK=1 --
   one "emb under autocast " SALUN_SD_EMB_FP32=0 --
   one "emb fp32, one SiLU " SALUN_SD_EMB_FP32=1 --
-  one "wgrad on main      " SALUN_BF16_WGRAD_OVERLAP=0 --
-  one "wgrad beside       " SALUN_BF16_WGRAD_OVERLAP=1 --
+  one "wgrad on main      " SALUN_WGRAD_OVERLAP=0 --
+  one "wgrad beside       " SALUN_WGRAD_OVERLAP=1 --
 done
 # data parallel at world size 1 (RCCL): with / without the target pass on a stream of its own (the tree's rule: without)
 export MASTER_PORT=29637

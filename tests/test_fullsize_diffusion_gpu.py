@@ -107,13 +107,13 @@ def test_sd_v1_bf16_full_size_unlearn_step():
     _check_masked_update(arena, opt, mask, theta0)
 
 
-def test_side_stream_backward_weight_never_changes_a_gradient_bit():
+def test_wgrad_side_stream_never_changes_a_gradient_bit():
     """Full-size CFG-DDPM U-Net, batch 128: every parameter gradient with backward-weight on the side stream equals,
     bit for bit and run after run, the single-stream result.  Round 4 found the one way it could differ: autograd
     accumulates the residual's second contribution INTO the gradient buffer (in place, main stream) that the first
     AttnBlock's proj_out backward-weight kernel was still reading on the side stream — visible once the own fp32
-    attention made that block's backward short (resblock.hold_until_join)."""
-    from unlearn_saliency_amd import resblock
+    attention made that block's backward short (wgrad_side.hold_until_join)."""
+    from unlearn_saliency_amd import wgrad_side
     from unlearn_saliency_amd.conv import use_salun_convs
     from unlearn_saliency_amd.DDPM.functions import load_config
     from unlearn_saliency_amd.DDPM.functions.losses import loss_registry_conditional
@@ -132,8 +132,8 @@ def test_side_stream_backward_weight_never_changes_a_gradient_bit():
     from unlearn_saliency_amd import ops
 
     def grads(overlap):
-        prev = resblock.OVERLAP_WGRAD
-        resblock.OVERLAP_WGRAD = overlap
+        prev = wgrad_side.OVERLAP
+        wgrad_side.OVERLAP = overlap
         ops.WGRAD_KERNEL[0] = "shared"   # the same backward-weight kernel on either schedule (round 6: a launch that does
         try:                             # not share the device takes the ring kernel — another summation order)
             torch.manual_seed(5)  # label drop
@@ -143,7 +143,7 @@ def test_side_stream_backward_weight_never_changes_a_gradient_bit():
             loss_registry_conditional["simple"](model, x, t, c, e, b).backward()
             torch.cuda.synchronize()
         finally:
-            resblock.OVERLAP_WGRAD = prev
+            wgrad_side.OVERLAP = prev
             ops.WGRAD_KERNEL[0] = None
         return arena.grads.clone()
 

@@ -20,7 +20,7 @@ import contextlib
 
 from .. import utils
 from ... import dist as sdist
-from ... import resblock
+from ... import wgrad_side
 
 
 def l1_regularization(model) -> torch.Tensor:
@@ -84,8 +84,8 @@ def run_pass(loader, model, criterion, optimizer, epoch: int, args, *,
 
         optimizer.zero_grad()
         # the l1 term gives every parameter a second gradient producer (AccumulateGrad on the main stream): the
-        # convolution kernels must then accumulate on the main stream too (resblock.overlap_disabled)
-        with (resblock.overlap_disabled() if l1_alpha else contextlib.nullcontext()):
+        # convolution kernels must then accumulate on the main stream too (wgrad_side.overlap_disabled)
+        with (wgrad_side.overlap_disabled() if l1_alpha else contextlib.nullcontext()):
             loss.backward()
         optimizer.step()
         if after_step is not None:

@@ -19,7 +19,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import dist as sdist
-from . import gradsink, ops, resblock, ringpack
+from . import gradsink, ops, ringpack, wgrad_side
 
 
 # calls that went to the library (MIOpen) instead of the MFMA kernels, by reason
@@ -90,22 +90,12 @@ class _ConvFn(FastFunction):
         if ctx.needs_input_grad[1]:
             dst = gradsink.sink(ctx.weight_param) if ctx.native else None
             # the weight gradient goes straight into .grad (gradsink): nothing on the main stream consumes it before
-            # the end of the backward pass, so it can run on the side stream next to backward-data (resblock.py)
-            # (also under data parallel: the slice's all-reduce waits for the side stream, dist.BucketedGradReducer)
-            overlap = (dst is not None and resblock.OVERLAP_WGRAD)
-            if overlap:
-                main, side = torch.cuda.current_stream(dy.device), resblock._side_stream(dy.device)
-                side.wait_stream(main)
-                with resblock._on_side(side, dst is None):
-                    dw = ops.conv2d_backward_weight(x, dy, w.shape, stride, pad, out=dst, accumulate=True, shared=True)
-                if dw is None:  # outside the kernel's domain after all: nothing was launched
-                    overlap = False
-                else:
-                    x.record_stream(side)
-                    dy.record_stream(side)
-                    resblock.hold_until_join(dy)  # autograd must not accumulate into dy in place while the side stream reads it
-                    resblock._join_at_end_of_backward(dy.device)
-            if not overlap:
+            # the end of the backward pass, so it can run on the side stream next to backward-data (wgrad_side.py)
+            if dst is not None and wgrad_side.OVERLAP:
+                dw = wgrad_side.beside(dy.device, (x, dy), lambda side: ops.conv2d_backward_weight(
+                    x, dy, w.shape, stride, pad, out=dst, accumulate=True, shared=True, stream=side))
+            # (None after the side-stream attempt: outside the kernel's domain, nothing was launched)
+            if dw is None:
                 dw = ops.conv2d_backward_weight(x, dy, w.shape, stride, pad, out=dst, accumulate=True) if ctx.native else None
             if dw is None:
                 _fallback("backward", f"backward-weight {tuple(x.shape)} * {tuple(w.shape)}")

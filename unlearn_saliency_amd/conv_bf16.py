@@ -23,7 +23,7 @@ import torch
 from .fastfn import FastFunction
 import torch.nn as nn
 
-from . import gradsink, ops
+from . import gradsink, ops, wgrad_side
 from .conv import SalunConv2d, _eligible
 
 
@@ -32,34 +32,11 @@ def _nhwc(t: torch.Tensor) -> torch.Tensor:
     return t.to(torch.bfloat16).contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1)
 
 
-# SALUN_BF16_WGRAD_OVERLAP=0: backward-weight (+ its reduce and the bias column sums) on the main stream, as in rounds 2 - 5
-_OVERLAP_BF16 = [_os_env.environ.get("SALUN_BF16_WGRAD_OVERLAP", "1") != "0"]
-
-
-def _wgrad_beside(dev, tensors, launch):
-    """Weight / bias gradients that go straight into `.grad` (gradsink) are consumed by nothing before the end of the
-    backward pass: issue `launch()` on the side stream resblock.py keeps for exactly this (scratch buffers are per stream,
-    ops.workspace; the stream has a hardware queue of its own, streams.py), next to the input-gradient kernels of this and
-    the following layers — at batch 8 most of the SD U-Net's kernels leave CUs idle.  The main stream joins once, at the
-    end of the backward pass (or, under data parallel, where the gradient slice is reduced: dist.BucketedGradReducer)."""
-    from . import resblock
-    main, side = torch.cuda.current_stream(dev.index), resblock._side_stream(dev)
-    side.wait_stream(main)
-    ops._STREAM_OVERRIDE[0] = side.cuda_stream  # instead of `with torch.cuda.stream(side)`: see ops._STREAM_OVERRIDE
-    try:
-        out = launch()
-    finally:
-        ops._STREAM_OVERRIDE[0] = None
-    for t in tensors:
-        t.record_stream(side)
-    resblock.hold_until_join(tensors[-1])  # dy: autograd must not accumulate into it in place while the side stream reads it
-    resblock._join_at_end_of_backward(dev)
-    return out
-
-
 def _can_overlap() -> bool:
-    from . import resblock
-    return _OVERLAP_BF16[0] and resblock.OVERLAP_WGRAD and not torch.cuda.is_current_stream_capturing()
+    """Weight / bias gradients that go straight into `.grad` (gradsink) are consumed by nothing before the end of the
+    backward pass: they are issued on the backward-weight side stream (wgrad_side.beside), next to the input-gradient
+    kernels of this and the following layers — at batch 8 most of the SD U-Net's kernels leave CUs idle."""
+    return wgrad_side.OVERLAP and not torch.cuda.is_current_stream_capturing()
 
 
 class _ConvBF16Fn(FastFunction):
@@ -100,9 +77,9 @@ class _ConvBF16Fn(FastFunction):
                 # on THIS stream right away, so its (small) sums are a launch of their own here
                 if dnb is not None:
                     ops.colsum_bf16(dyn, dyn.shape[0], nbias_out=dnb)
-                _wgrad_beside(dyn.device, (xn, dyn),
-                              lambda: ops.conv2d_bf16_backward_weight(xn, dyn, wshape, s, p, out=dst, accumulate=True,
-                                                                      bias_out=bdst))
+                wgrad_side.beside(dyn.device, (xn, dyn),
+                                  lambda side: ops.conv2d_bf16_backward_weight(xn, dyn, wshape, s, p, out=dst,
+                                                                               accumulate=True, bias_out=bdst, stream=side))
             else:
                 got = ops.conv2d_bf16_backward_weight(xn, dyn, wshape, s, p, out=dst, accumulate=True, bias_out=bdst,
                                                       nbias_out=dnb)
@@ -272,11 +249,11 @@ class _LinearBF16Fn(FastFunction):
             if ctx.has_bias and bdst is None:
                 bdst = torch.zeros(K, dtype=torch.float32, device=dy2.device)
                 db = bdst
-            launch = lambda: ops.conv2d_bf16_backward_weight(as_img(x2, C), as_img(dy2, K), (K, C, 1, 1), 1, 0,
-                                                             out=dst.view(K, C, 1, 1) if dst is not None else None,
-                                                             accumulate=True, bias_out=bdst)
+            launch = lambda side=None: ops.conv2d_bf16_backward_weight(
+                as_img(x2, C), as_img(dy2, K), (K, C, 1, 1), 1, 0, out=dst.view(K, C, 1, 1) if dst is not None else None,
+                accumulate=True, bias_out=bdst, stream=side)
             if dst is not None and db is None and _can_overlap():
-                _wgrad_beside(dy2.device, (x2, dy2), launch)
+                wgrad_side.beside(dy2.device, (x2, dy2), launch)
             else:
                 got = launch()
                 if dst is None:

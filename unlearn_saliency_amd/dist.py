@@ -17,6 +17,8 @@ from typing import Optional
 import torch
 import torch.distributed as dist
 
+from . import wgrad_side
+
 
 def is_dist() -> bool:
     return dist.is_available() and dist.is_initialized()
@@ -176,12 +178,6 @@ def shard_loss_scale(loader) -> float:
     return (hi - lo) * ws / float(b)
 
 
-def _wgrad_side_stream(device):
-    """The backward-weight side stream of `device` if one was ever created (resblock.py), else None."""
-    from . import resblock
-    return resblock._side_streams.get(device)
-
-
 class BucketedGradReducer:
     """Overlap the per-step gradient all-reduce with backward.
 
@@ -251,7 +247,7 @@ class BucketedGradReducer:
         self._order.append(b)
         if dist.get_backend() == "nccl":
             # The weight-gradient kernels of this slice may still be queued on the backward-weight side stream
-            # (resblock.py / conv.py / conv_bf16.py overlap them with backward-data).  The collective must wait for them —
+            # (wgrad_side.py overlaps them with backward-data).  The collective must wait for them —
             # but the MAIN stream must not: a join per block (rounds 1 - 5) cost the data-parallel step 17 % at world size
             # 1 (10.0 vs 8.5 ms).  So the collective is issued FROM THE SIDE STREAM, after that stream has been told to
             # wait for the main stream's work so far (the normalisation / bias gradients of the slice; the side stream lags
@@ -262,7 +258,7 @@ class BucketedGradReducer:
             # from the side stream 8.60 ms in both.  A rare 12.4 ms state — ~3 % of processes, decided at start-up, cause
             # unknown — exists with either form: profiles/r06_dp_outliers.txt.)
             dev = sl.device
-            side = _wgrad_side_stream(dev)
+            side = wgrad_side.existing_stream(dev)
             if side is None:
                 self.works.append((dist.all_reduce(sl, op=dist.ReduceOp.AVG, async_op=True), None))
             else:
@@ -271,7 +267,7 @@ class BucketedGradReducer:
                     self.works.append((dist.all_reduce(sl, op=dist.ReduceOp.AVG, async_op=True), None))
         else:
             if sl.is_cuda:  # gloo stages device tensors through the host behind the CURRENT stream only
-                side = _wgrad_side_stream(sl.device)
+                side = wgrad_side.existing_stream(sl.device)
                 if side is not None:
                     torch.cuda.current_stream(sl.device).wait_stream(side)
             self.works.append((dist.all_reduce(sl, op=dist.ReduceOp.SUM, async_op=True), sl))

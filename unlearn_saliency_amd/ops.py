@@ -21,20 +21,10 @@ _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 _cur_device = getattr(torch._C, "_cuda_getDevice", None)
 
 
-# Set (to a raw stream handle) around calls that must be issued on another stream than torch's current one WITHOUT paying
-# for `with torch.cuda.stream(...)` (~10 us of host time per use; conv_bf16._wgrad_beside issues 470 backward-weight calls
-# per SD step on the side stream and the step is host-bound).  Only the wrappers of this module look at it: a wrapper
-# that allocates its result with torch must not be called under an override (the allocation would belong to the current
-# stream) — backward-weight into `.grad` storage allocates nothing but the per-stream scratch buffer.
-_STREAM_OVERRIDE = [None]
-
-
 def _stream_handle(idx: Optional[int] = None) -> int:
     """The raw handle of device `idx`'s (default: the current device's) current stream — what
     `torch.cuda.current_stream(idx).cuda_stream` returns, without building a Stream object and re-probing the device on
     each of ~4,500 calls per SD step."""
-    if _STREAM_OVERRIDE[0] is not None:
-        return _STREAM_OVERRIDE[0]
     if _raw_stream is None or _cur_device is None:
         return torch.cuda.current_stream(idx).cuda_stream
     return _raw_stream(_cur_device() if idx is None else idx)
@@ -74,21 +64,25 @@ def _q(name: str, *args):
 
 
 # One scratch buffer per (device, stream), grown on demand: reuse is ordered by the stream the kernels run on, so
-# work issued on a side stream (resblock.py overlaps backward-weight with backward-data) never shares scratch with
+# work issued on a side stream (wgrad_side.py overlaps backward-weight with backward-data) never shares scratch with
 # the main stream.
 _ws: dict[tuple, torch.Tensor] = {}
 
 
-def workspace(nbytes: int, device: torch.device, tag: str = "") -> torch.Tensor:
+def workspace(nbytes: int, device: torch.device, tag: str = "",
+              stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
     """`tag` separates buffers whose contents must survive other ops' scratch use (the top-k publication block is
-    read back by mask_topk_thresholds after arbitrary calls in between)."""
+    read back by mask_topk_thresholds after arbitrary calls in between).  `stream`: the stream the kernels run on
+    (default: the current one); a buffer grown for another stream is allocated under it, so that the caching allocator
+    hands the outgrown block back to that stream only."""
     idx = device.index if device.index is not None else torch.cuda.current_device()
     # the top-k publication block is keyed by the device alone: mask_topk_status / mask_topk_thresholds must find the
     # block the last mask_topk call wrote whatever stream is current when they are called (side streams exist)
-    key = (idx, None if tag == "topk" else _stream_handle(idx), tag)
+    key = (idx, None if tag == "topk" else _stream_handle(idx) if stream is None else stream.cuda_stream, tag)
     w = _ws.get(key)
     if w is None or w.numel() < nbytes:
-        w = torch.empty(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=device)
+        with torch.cuda.stream(stream):  # (None: a no-op)
+            w = torch.empty(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=device)
         _ws[key] = w
     return w
 
@@ -437,10 +431,11 @@ WGRAD_KERNEL = [None]
 
 def conv2d_backward_weight(x: torch.Tensor, dy: torch.Tensor, w_shape, stride: int, pad: int,
                            out: Optional[torch.Tensor] = None, accumulate: bool = False,
-                           shared: bool = False) -> Optional[torch.Tensor]:
+                           shared: bool = False, stream: Optional[torch.cuda.Stream] = None) -> Optional[torch.Tensor]:
     """dw = backward_weight(x, dy); with `out` the result is written (accumulate=False) or added
     (accumulate=True) into that tensor — e.g. the parameter's slice of the flat gradient arena.  `shared`: the launch
-    runs on a side stream beside other kernels of the step (SALUN_WGRAD_SHARED: kernel choice, include/salun.h)."""
+    runs on a side stream beside other kernels of the step (SALUN_WGRAD_SHARED: kernel choice, include/salun.h).
+    `stream`: where the kernel runs (default: the current stream; wgrad_side.beside passes the side stream)."""
     N, C, H, W = x.shape
     K, _, R, _ = w_shape
     P, Q = dy.shape[2], dy.shape[3]
@@ -448,14 +443,15 @@ def conv2d_backward_weight(x: torch.Tensor, dy: torch.Tensor, w_shape, stride: i
     nbytes = L.salun_conv2d_wgrad_workspace_bytes(N, C, K, R, P, Q)
     if nbytes == 0:
         return None
-    ws = workspace(nbytes, x.device)
+    ws = workspace(nbytes, x.device, stream=stream)
     dw = out if out is not None else torch.empty(tuple(w_shape), dtype=torch.float32, device=x.device)
     rc = L.salun_conv2d_backward_weight_ex(_dev(x, torch.float32, "x"), _dev(dy, torch.float32, "dy"),
                                            _dev(dw, torch.float32, "dw"), N, C, H, W, K, R, stride, pad, P, Q,
                                            int(bool(accumulate and out is not None)),
                                            _lib.SALUN_WGRAD_SHARED if (shared if WGRAD_KERNEL[0] is None
                                                                        else WGRAD_KERNEL[0] == "shared") else 0,
-                                           c_void_p(ws.data_ptr()), c_size_t(ws.numel()), _stream())
+                                           c_void_p(ws.data_ptr()), c_size_t(ws.numel()),
+                                           c_void_p(_stream_handle() if stream is None else stream.cuda_stream))
     if rc == _lib.SALUN_EINVAL:
         return None
     check(rc, "salun_conv2d_backward_weight")
@@ -593,17 +589,18 @@ def conv2d_bf16_backward_data(dy: torch.Tensor, wp: torch.Tensor, x_shape, R: in
 def conv2d_bf16_backward_weight(x: torch.Tensor, dy: torch.Tensor, w_shape, stride: int, pad: int,
                                 out: Optional[torch.Tensor] = None, accumulate: bool = False,
                                 bias_out: Optional[torch.Tensor] = None,
-                                nbias_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                                nbias_out: Optional[torch.Tensor] = None,
+                                stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
     """dw fp32 OIHW (written, or added into `out` when accumulate); `bias_out` (fp32 [K]) receives / accumulates the
     per-channel sum of dy in the same call; `nbias_out` (fp32 [N, K], N <= 128) is overwritten with the per-image channel
-    sums of dy — the gradient of the forward's `nbias` term."""
+    sums of dy — the gradient of the forward's `nbias` term.  `stream` as for conv2d_backward_weight."""
     N, H, W, C = x.shape
     K, _, R, _ = w_shape
     L = _lib.lib()
     nbytes = _q("salun_conv2d_bf16_wgrad_workspace_bytes", N, H, W, C, K, R, stride, pad)
     if nbytes == 0:
         raise ValueError(f"bf16 backward-weight: unsupported shape C={C} K={K} R={R} stride={stride} pad={pad}")
-    ws = workspace(nbytes, x.device)
+    ws = workspace(nbytes, x.device, stream=stream)
     dw = out if out is not None else torch.empty(tuple(w_shape), dtype=torch.float32, device=x.device)
     if nbias_out is not None and tuple(nbias_out.shape) != (N, K):
         raise ValueError(f"nbias_out must be [{N}, {K}]")
@@ -611,7 +608,8 @@ def conv2d_bf16_backward_weight(x: torch.Tensor, dy: torch.Tensor, w_shape, stri
                                                  _dev(dw, torch.float32, "dw"), _dev(bias_out, torch.float32, "db", True),
                                                  _dev(nbias_out, torch.float32, "dnb", True),
                                                  N, H, W, C, K, R, stride, pad, int(bool(accumulate and out is not None)),
-                                                 c_void_p(ws.data_ptr()), c_size_t(ws.numel()), _stream()),
+                                                 c_void_p(ws.data_ptr()), c_size_t(ws.numel()),
+                                                 c_void_p(_stream_handle() if stream is None else stream.cuda_stream)),
           "salun_conv2d_bf16_backward_weight_ex")
     return dw
 

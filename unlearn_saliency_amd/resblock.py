@@ -6,7 +6,8 @@
 Forward is 2-3 MFMA convolutions + 2-3 fused BN launches; backward walks the same chain by hand:
 the residual branch's gradient is folded into conv1's backward-data epilogue (`addend`) instead of a separate
 add pass over the activation, and all weight / BN gradients are accumulated by their kernels directly into the
-parameters' `.grad` storage (gradsink.py) — no AccumulateGrad launches.  Per block that removes one
+parameters' `.grad` storage (gradsink.py) — no AccumulateGrad launches; the weight gradients on the backward-weight side
+stream (wgrad_side.py).  Per block that removes one
 3-pass elementwise add over the block input and 6-9 small adds, plus the autograd bookkeeping of ~10 nodes.
 In forward the projection branch bn_d(conv_d(x)) of a strided block (a 1x1 stride-2 convolution at 13 - 50 TFLOP/s and a
 small BatchNorm: launches that leave most of the chip idle) is issued on the side stream beside conv1 -> bn1 -> conv2
@@ -26,126 +27,9 @@ import torch.nn as nn
 import os
 
 from . import dist as sdist
-from . import draws, gradsink, ops, streams
+from . import draws, gradsink, ops, wgrad_side
 
-# Backward-weight and backward-data of one convolution depend on the same dY and on nothing of each other.  The
-# backward-weight kernel runs ONE wave per SIMD (register budget) and leaves LDS for a second workgroup, so issuing it
-# on a side stream lets the two kernels share the CUs — the matrix pipes idle less than when either runs alone.
-# SALUN_WGRAD_OVERLAP=0 keeps everything on one stream.
-OVERLAP_WGRAD = os.environ.get("SALUN_WGRAD_OVERLAP", "1") != "0"
 FWD_SHORTCUT_BESIDE = os.environ.get("SALUN_FWD_SHORTCUT_BESIDE", "1") != "0"  # _BasicBlockFn.forward
-
-
-class overlap_disabled:
-    """Context manager: keep backward-weight on the main stream.  Needed whenever something else than the
-    convolution kernels writes a parameter's `.grad` during the same backward pass — e.g. the l1 penalty of FT_l1 /
-    GA_l1 (`_steps.l1_regularization`), whose AccumulateGrad `w.grad.add_()` runs on the main stream and would race
-    with a side-stream `salun_conv2d_backward_weight` accumulating into the same slice."""
-
-    def __enter__(self):
-        global OVERLAP_WGRAD
-        self._prev = OVERLAP_WGRAD
-        OVERLAP_WGRAD = False
-        return self
-
-    def __exit__(self, *exc):
-        global OVERLAP_WGRAD
-        OVERLAP_WGRAD = self._prev
-        return False
-
-
-def reset_join_state() -> None:
-    """Forget a pending end-of-backward join (only needed after a backward pass was aborted by an exception) and make
-    the current streams wait for whatever the side streams still have in flight."""
-    _join_queued.clear()
-    _held.clear()
-    for dev, side in _side_streams.items():
-        torch.cuda.current_stream(dev).wait_stream(side)
-_side_streams: dict = {}
-
-
-def _side_stream(device: torch.device) -> "torch.cuda.Stream":
-    s = _side_streams.get(device)
-    if s is None:
-        s = _side_streams[device] = streams.concurrent_stream(device)
-    return s
-
-
-class _on_side:
-    """`with torch.cuda.stream(side)` for a call that allocates nothing with torch (the gradient goes into `.grad` storage):
-    the wrappers of ops.py are handed the raw handle instead (ops._STREAM_OVERRIDE) — ~10 us of host time less per use, 20
-    uses per ResNet-18 step, which the data-parallel step (hooks and slice launches on top) feels.  With `alloc` (no sink:
-    the result is a fresh tensor that must belong to the side stream) the ordinary stream context is entered."""
-
-    __slots__ = ("side", "ctx")
-
-    def __init__(self, side, alloc: bool):
-        self.side = side
-        self.ctx = torch.cuda.stream(side) if alloc else None
-
-    def __enter__(self):
-        if self.ctx is not None:
-            return self.ctx.__enter__()
-        ops._STREAM_OVERRIDE[0] = self.side.cuda_stream
-
-    def __exit__(self, *exc):
-        if self.ctx is not None:
-            return self.ctx.__exit__(*exc)
-        ops._STREAM_OVERRIDE[0] = None
-        return False
-
-
-_join_queued: set = set()
-# Gradient tensors a side-stream kernel is still reading.  autograd OWNS a gradient buffer once every node it was handed
-# to has returned, and accumulates further contributions into it IN PLACE when nobody else holds it
-# (InputBuffer::add: `old.add_(new)` if use_count == 1) — on the main stream, while the side stream may still be reading
-# it: `record_stream` guards against reuse after free, not against that write.  A held reference makes the engine
-# accumulate out of place.  Found in round 4 (the first AttnBlock's proj_out weight gradient changed from run to run
-# once the attention's backward became short enough for the residual's accumulation to overtake the 1x1 backward-weight).
-_held: dict = {}
-
-
-def hold_until_join(t: torch.Tensor) -> None:
-    """Keep `t` referenced until the side stream has passed the kernels enqueued on it so far, at the latest until the
-    end-of-backward join.  One event per EIGHT tensors (an event per tensor was 11 us of host time on each of ~470
-    backward-weight launches of an SD step): a batch is released when the event recorded behind its last member has
-    completed.  Inside a stream capture events cannot be queried: the references simply live until the join."""
-    st = _held.get(t.device)
-    if st is None:
-        st = _held[t.device] = {"open": [], "closed": []}
-    st["open"].append(t)
-    if len(st["open"]) < 8 or torch.cuda.is_current_stream_capturing():
-        return
-    ev = torch.cuda.Event()
-    ev.record(_side_stream(t.device))
-    st["closed"].append((ev, st["open"]))
-    st["open"] = []
-    closed = st["closed"]
-    while closed and closed[0][0].query():
-        closed.pop(0)
-
-
-def release_held(device) -> None:
-    """After the main stream has been made to wait for the side stream: nothing is being read there any more."""
-    _held.pop(device, None)
-
-
-def _join_at_end_of_backward(device: torch.device) -> None:
-    """Single process: the main stream waits for the side stream ONCE, when the whole backward pass has been issued
-    (autograd's end-of-backward callback) — so after `loss.backward()` returns, gradients are ordered on the current
-    stream as usual, and inside the pass the weight-gradient kernels of one block overlap the next block's work.
-    Caveat: if a backward pass dies with an exception the engine drops its callbacks; call `reset_join_state()` (or
-    set SALUN_WGRAD_OVERLAP=0) before reusing the process after such a failure."""
-    if device in _join_queued:
-        return
-    _join_queued.add(device)
-
-    def _join():
-        _join_queued.discard(device)
-        torch.cuda.current_stream(device).wait_stream(_side_stream(device))
-        _held.pop(device, None)
-
-    torch.autograd.Variable._execution_engine.queue_callback(_join)
 
 
 def _bn_args(bn: nn.BatchNorm2d):
@@ -166,10 +50,11 @@ class _BasicBlockFn(FastFunction):
                 cd_ = ops.conv2d_forward(x, wd, None, s, 0, P, Q)
                 return (cd_,) + tuple(ops.bn_forward(cd_, None, gd, bd, *_bn_args(blk.downsample[1]), False,
                                                      blk.downsample[1].num_batches_tracked))
-            if FWD_SHORTCUT_BESIDE and OVERLAP_WGRAD and x.is_cuda and not torch.cuda.is_current_stream_capturing():
+            if (FWD_SHORTCUT_BESIDE and wgrad_side.OVERLAP and x.is_cuda
+                    and not torch.cuda.is_current_stream_capturing()):
                 # the 1x1 stride-2 projection + its BatchNorm depend on x alone: issued on the (idle, in forward)
                 # backward-weight side stream beside conv1 -> bn1 -> conv2, joined before bn2 adds the result
-                main, fork = torch.cuda.current_stream(x.device), _side_stream(x.device)
+                main, fork = torch.cuda.current_stream(x.device), wgrad_side.stream(x.device)
                 fork.wait_stream(main)
                 with torch.cuda.stream(fork):
                     cd, skip, md, idd = shortcut()
@@ -209,22 +94,16 @@ class _BasicBlockFn(FastFunction):
                 dg = db = None
             return dx, dres, dg, db
 
-        main = torch.cuda.current_stream(dout.device)
-        side = _side_stream(dout.device) if OVERLAP_WGRAD else None
+        dev = dout.device
+        overlap = wgrad_side.OVERLAP
 
         def wgrad(xin, dy, w, stride, pad):
             dst = gradsink.sink(w)
-            if side is None:
-                dw = ops.conv2d_backward_weight(xin, dy, w.shape, stride, pad, out=dst, accumulate=True)
+            if overlap:
+                dw = wgrad_side.beside(dev, (xin, dy), lambda side: ops.conv2d_backward_weight(
+                    xin, dy, w.shape, stride, pad, out=dst, accumulate=True, shared=True, stream=side), alloc=dst is None)
             else:
-                side.wait_stream(main)  # dy (and everything before it) is complete for the side stream
-                with _on_side(side, dst is None):
-                    dw = ops.conv2d_backward_weight(xin, dy, w.shape, stride, pad, out=dst, accumulate=True, shared=True)
-                for t in (xin, dy):  # freed when this backward returns: keep the memory until the side stream is done
-                    t.record_stream(side)
-                hold_until_join(dy)  # ... and keep autograd from accumulating into it in place meanwhile
-                if dst is None and dw is not None:
-                    dw.record_stream(main)
+                dw = ops.conv2d_backward_weight(xin, dy, w.shape, stride, pad, out=dst, accumulate=True)
             if dst is not None:
                 gradsink.arrived(w)
                 return None
@@ -246,15 +125,10 @@ class _BasicBlockFn(FastFunction):
         dc1, _, dg1, db1 = bn_bwd(dy1, y1, c1, g1, b1, m1, i1, True, False)
         dw1 = wgrad(x, dc1, w1, s, 1)
         dx = ops.conv2d_backward_data(dc1, w1, x.shape, s, 1, addend=dxd) if ctx.needs_input_grad[0] else None
-        if side is not None:
-            if not all(g is None for g in (dw1, dw2, dwd)):
-                # autograd route: AccumulateGrad consumes the returned tensors on the main stream -> join now.
-                # (Data parallel needs no join here any more: a gradient slice's all-reduce waits for the side stream
-                # itself — dist.BucketedGradReducer._launch.)
-                main.wait_stream(side)
-                release_held(dout.device)
-            else:
-                _join_at_end_of_backward(dout.device)
+        if overlap and not all(g is None for g in (dw1, dw2, dwd)):
+            # autograd route: AccumulateGrad consumes the returned tensors on the main stream -> join now
+            torch.cuda.current_stream(dev).wait_stream(wgrad_side.stream(dev))
+            wgrad_side.release_held(dev)
         return dx, None, dw1, dg1, db1, dw2, dg2, db2, dwd, dgd, dbd
 
 
@@ -365,23 +239,17 @@ class _DiffusionResnetBlockFn(FastFunction):
         x, a1, c1, a2, n1w, n1b, w1, b1, n2w, n2b, w2, b2, ws, bs, m1, r1, m2, r2 = ctx.saved_tensors
         G1, G2, p, dkey = ctx.cfg
         dout = dout.contiguous()
-        main = torch.cuda.current_stream(dout.device)
-        side = _side_stream(dout.device) if OVERLAP_WGRAD else None
+        dev = dout.device
+        overlap = wgrad_side.OVERLAP
         returned = []  # weight gradients handed back to autograd (no sink): they need the main stream to have joined
 
         def wgrad(xin, dy, w, pad):
             dst = gradsink.sink(w)
-            if side is None:
-                dw = ops.conv2d_backward_weight(xin, dy, w.shape, 1, pad, out=dst, accumulate=True)
+            if overlap:
+                dw = wgrad_side.beside(dev, (xin, dy), lambda side: ops.conv2d_backward_weight(
+                    xin, dy, w.shape, 1, pad, out=dst, accumulate=True, shared=True, stream=side), alloc=dst is None)
             else:
-                side.wait_stream(main)
-                with _on_side(side, dst is None):
-                    dw = ops.conv2d_backward_weight(xin, dy, w.shape, 1, pad, out=dst, accumulate=True, shared=True)
-                for t in (xin, dy):
-                    t.record_stream(side)
-                hold_until_join(dy)
-                if dst is None and dw is not None:
-                    dw.record_stream(main)
+                dw = ops.conv2d_backward_weight(xin, dy, w.shape, 1, pad, out=dst, accumulate=True)
             if dst is not None:
                 gradsink.arrived(w)
                 return None
@@ -439,12 +307,9 @@ class _DiffusionResnetBlockFn(FastFunction):
             dx = ops.conv2d_backward_data(dout, ws, x.shape, 1, pad, addend=dxg)
         if gw is not None:
             dg1 = dbt1 = None
-        if side is not None:
-            if returned:
-                main.wait_stream(side)
-                release_held(dout.device)
-            else:
-                _join_at_end_of_backward(dout.device)
+        if overlap and returned:
+            torch.cuda.current_stream(dev).wait_stream(wgrad_side.stream(dev))
+            wgrad_side.release_held(dev)
         if not ctx.needs_input_grad[0]:
             dx = None
         return dx, dproj, None, dg1, dbt1, dw1, db1, dg2, dbt2, dw2, db2, dws, dbs

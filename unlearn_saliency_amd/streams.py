@@ -3,7 +3,7 @@
 HIP maps every stream onto one of a few hardware queues (4 by default); two streams on the same
 queue execute strictly one after the other.  Single-process runs got lucky — the current stream and the first
 `torch.cuda.Stream()` landed on different queues — but with a process group the RCCL communicator's own streams shift
-the assignment, and the backward-weight side stream of resblock.py ended up on the MAIN stream's queue: the
+the assignment, and the backward-weight side stream (wgrad_side.py) ended up on the MAIN stream's queue: the
 data-parallel ResNet-18 step ran every kernel back to back, 10.03 ms instead of 8.53 (round 6,
 `bench.py --force_collectives`; with eight hardware queues the same run took 8.66 ms).
 

@@ -164,7 +164,7 @@ def test_forget_and_target_on_host_tensors_is_the_plain_sequence():
 
 def test_registered_modules_repack_together_once_per_parameter_epoch():
     """Round 6: after an optimizer step every weight image of a model is stale; the first one asked for re-packs ALL of
-    them in one batch (conv_bf16._repack_stale -> ops.bf16_pack_batch), later requests are cache hits; a second model's
+    them in one batch (weightimg.image -> ops.bf16_pack_batch), later requests are cache hits; a second model's
     modules on another device are not touched; a torch write on one weight re-packs that weight alone."""
     from unlearn_saliency_amd import conv_bf16, ops
     from unlearn_saliency_amd.SD.unet import UNetModel
@@ -172,7 +172,8 @@ def test_registered_modules_repack_together_once_per_parameter_epoch():
     n_conv = conv_bf16.use_salun_convs_bf16(m)
     n_lin = conv_bf16.use_salun_linears_bf16(m)
     mods = [x for x in m.modules() if isinstance(x, (conv_bf16.SalunConv2dBF16, conv_bf16.SalunLinearBF16))]
-    assert len(mods) == n_conv + n_lin and all(getattr(x, "_salun_pack_registered", False) for x in mods)
+    assert len(mods) == n_conv + n_lin and all(i is not None and i.registered for x in mods
+                                             for i in ([x._img, x._img_t] if isinstance(x, conv_bf16.SalunLinearBF16) else [x._img]))
     batches = []
     real = ops.bf16_pack_batch
     ops.bf16_pack_batch = lambda jobs: batches.append(list(jobs)) or 1

@@ -23,7 +23,7 @@ import torch
 import yaml
 
 from .. import dist as sdist
-from .. import draws, hostperf, ops
+from .. import draws, hostperf, ops, weightimg
 from ..flat import FlatArena
 from ..optim import FusedMaskedAdam
 from ..streams import concurrent_stream
@@ -164,9 +164,9 @@ def forget_and_target(model, z_noisy, t, c_forget, c_target):
         side = _target_streams[dev] = concurrent_stream(dev)
     main = torch.cuda.current_stream(dev)
     side.wait_stream(main)
-    packs = ops.PACK_CALLS[0]
+    packs = weightimg.BF16_LAUNCHES[0]   # (no event orders a bf16 pack against the side stream: weightimg.Registry)
     out = model.apply_model(z_noisy, t, c_forget)
-    if ops.PACK_CALLS[0] != packs:
+    if weightimg.BF16_LAUNCHES[0] != packs:
         with torch.no_grad():
             return out, model.apply_model(z_noisy, t, c_target)
     with torch.no_grad(), torch.cuda.stream(side):

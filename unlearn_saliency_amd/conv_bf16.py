@@ -6,8 +6,8 @@ modules of SD/ldm/modules/diffusionmodules/openaimodel.py and SD/ldm/modules/att
 the fp32 master weights stay views of the flat arena).  Such a module
 
   * takes any 4-D device tensor, views it as bf16 NHWC (`channels_last` — a no-op for tensors these modules produced),
-  * reads a bf16 image of its weight that is re-packed only when the master weights changed (`ops.PARAM_EPOCH`, bumped
-    by the fused optimizer kernels, plus torch's own version counter),
+  * reads a bf16 image of its weight that is re-packed only when the master weights changed (weightimg.py: the
+    parameter epoch the fused optimizer kernels bump, torch's version counters, the parameter's address),
   * returns a bf16 `channels_last` tensor (logical NCHW shape, so the surrounding model code is unchanged),
   * in backward writes dX in bf16 and adds dW / db in fp32 straight into the parameters' `.grad` views (gradsink.py).
 
@@ -17,13 +17,14 @@ run on the fp32 MFMA kernels of conv.py; nothing here calls the library convolut
 from __future__ import annotations
 
 import os as _os_env
+import weakref as _weakref
 
 import torch
 
 from .fastfn import FastFunction
 import torch.nn as nn
 
-from . import gradsink, ops, wgrad_side
+from . import gradsink, ops, weightimg, wgrad_side
 from .conv import SalunConv2d, _eligible
 
 
@@ -99,80 +100,55 @@ class _ConvBF16Fn(FastFunction):
 # ------------------------------------------------------------------------------------------- weight images
 # After an optimizer step EVERY bf16 weight image of a model is stale.  One pack launch per layer at its first use was
 # 256 launches of ~13 us per SD step (round 5 profile: 1.4 % of the device time, most launches far too small to fill the
-# chip); the modules `use_salun_convs_bf16` / `use_salun_linears_bf16` re-classed are therefore REGISTERED, and the first
-# stale image any of them asks for re-packs all stale images of that device in ceil(n / 64) launches (csrc:
-# k_pack_jobs).  A module that was never registered (built by hand in a test) packs alone, as before.
-import weakref as _weakref
-
-_REGISTERED: list = []      # weak references, in registration order (the order of use in a forward pass)
-_IS_REGISTERED = "_salun_pack_registered"
+# chip); the images of the modules `use_salun_convs_bf16` / `use_salun_linears_bf16` re-classed are therefore REGISTERED
+# (weightimg.py: the staleness rule and the batch), and the first stale one any of them asks for re-packs all stale
+# images of that device in ceil(n / 64) launches (csrc: k_pack_jobs).  A module that was never registered (built by hand
+# in a test) packs alone, as before.  No event orders a pack against other streams: SD/train_scripts.forget_and_target
+# watches PACK_LAUNCHES instead and keeps the target pass on the main stream when the forget pass packed anything.
 BATCH_PACKS = [_os_env.environ.get("SALUN_BF16_BATCH_PACK", "1") != "0"]  # A/B switch: False = one launch per image at its first use
-PACK_LAUNCHES = [0]
+PACK_LAUNCHES = weightimg.BF16_LAUNCHES
+# (the ops.* seams are looked up per call: host tests replace them)
+_IMAGES = weightimg.Registry(lambda jobs: ops.bf16_pack_batch(jobs), PACK_LAUNCHES, per_device=True, batching=BATCH_PACKS)
 
 
-def _register(mod) -> None:
-    if not getattr(mod, _IS_REGISTERED, False):
-        setattr(mod, _IS_REGISTERED, True)
-        _REGISTERED.append(_weakref.ref(mod))
+def _kcr(w):
+    """(K, C, R) of a convolution's OIHW or a Linear layer's [K, C] weight."""
+    return w.shape[0], w.shape[1], (w.shape[2] if w.dim() == 4 else 1)
 
 
-def _weight_key(w):
-    # PARAM_EPOCH: bumped by every kernel that rewrites parameters through raw pointers; w._version: torch writes
-    # on the parameter itself; the flat arena's version: torch writes on `arena.params` (or any slice of it) do
-    # NOT bump the parameter's own counter — `p.data = view` gave it a separate one (flat.py)
-    flat = getattr(w, "_salun_flat", None)
-    return (ops.PARAM_EPOCH[0], w._version, w.data_ptr(), flat._version if flat is not None else -1)
+def _alloc(w):
+    K, C, R = _kcr(w)
+    return torch.empty((K, R * R, C), dtype=torch.bfloat16, device=w.device)
 
 
-def _repack_stale(device) -> None:
-    """Every registered module on `device` whose image(s) do not match its weight: one batch on the current stream."""
-    jobs, done, alive = [], [], []
-    for ref in _REGISTERED:
-        mod = ref()
-        if mod is None:
-            continue
-        alive.append(ref)
-        w = mod.weight
-        if w.device != device:
-            continue
-        key = _weight_key(w)
-        lin = isinstance(mod, SalunLinearBF16)
-        K, C = w.shape[0], w.shape[1]
-        R = 1 if lin else mod.kernel_size[0]
-        if mod._pack is None or mod._pack_key != key or mod._pack.device != device:
-            if mod._pack is None or mod._pack.device != device:
-                mod._pack = torch.empty((K, R * R, C), dtype=torch.bfloat16, device=device)
-            jobs.append((w.detach(), mod._pack, K, C, R, False))
-            done.append((mod, "_pack_key", key))
-        if lin and (mod._pack_t is None or mod._pack_t_key != key or mod._pack_t.device != device):
-            if mod._pack_t is None or mod._pack_t.device != device:
-                mod._pack_t = torch.empty((C, K), dtype=torch.bfloat16, device=device)
-            jobs.append((w.detach(), mod._pack_t, K, C, 1, True))
-            done.append((mod, "_pack_t_key", key))
-    if len(alive) != len(_REGISTERED):
-        _REGISTERED[:] = alive
-    PACK_LAUNCHES[0] += ops.bf16_pack_batch(jobs)
-    for mod, attr, key in done:
-        setattr(mod, attr, key)
+def _alone(w, buf):
+    K, C, R = _kcr(w)
+    return ops.conv2d_bf16_pack(w.detach().view(K, C, R, R), buf)
+
+
+# attribute of the module -> kind: the [K, R*R, C] image, and the transposed [C, K] one of a Linear layer
+_KINDS = {
+    "_img": weightimg.Kind(_alloc, lambda w, buf: (w.detach(), buf, *_kcr(w), False), _alone),
+    "_img_t": weightimg.Kind(lambda w: torch.empty((w.shape[1], w.shape[0]), dtype=torch.bfloat16, device=w.device),
+                             lambda w, buf: (w.detach(), buf, w.shape[0], w.shape[1], 1, True),
+                             lambda w, buf: ops.pack_bf16(w.detach(), True, buf)),
+}
+
+
+def _slot(mod, attr: str, registered: bool = False) -> weightimg.Image:
+    """The image `attr` of `mod`, made at its first use (re-classed modules never ran an __init__ of ours)."""
+    img = weightimg.Image(_KINDS[attr], _IMAGES, lambda ref=_weakref.ref(mod): getattr(ref(), "weight", None), registered)
+    setattr(mod, attr, img)
+    return img
 
 
 class SalunConv2dBF16(nn.Conv2d):
     """Same parameters / state_dict as nn.Conv2d; device tensors go through the bf16 MFMA kernels."""
 
-    _pack = None
-    _pack_key = None
+    _img = None
 
     def packed_weight(self) -> torch.Tensor:
-        w = self.weight
-        key = _weight_key(w)
-        if self._pack is None or self._pack_key != key or self._pack.device != w.device:
-            if BATCH_PACKS[0] and getattr(self, _IS_REGISTERED, False):
-                _repack_stale(w.device)
-            else:
-                self._pack = ops.conv2d_bf16_pack(w.detach(), self._pack if self._pack is not None and self._pack.device == w.device else None)
-                self._pack_key = key
-                PACK_LAUNCHES[0] += 1
-        return self._pack
+        return weightimg.image(self._img or _slot(self, "_img"), self.weight)
 
     def forward(self, x, nbias=None, addend=None):
         """`nbias` ([N, K] fp32, e.g. a ResBlock's time-embedding term) and `addend` (a tensor of the output's shape,
@@ -275,42 +251,16 @@ class SalunLinearBF16(nn.Linear):
     """Same parameters / state_dict as nn.Linear.  Device inputs in the bf16 configuration (a bf16 tensor, or any
     tensor under bf16 autocast) go through the bf16 MFMA kernels; anything else is the plain fp32 F.linear."""
 
-    _pack = None
-    _pack_key = None
-    _pack_t = None
-    _pack_t_key = None
-
-    def _key(self):
-        return _weight_key(self.weight)
+    _img = None
+    _img_t = None
 
     def packed_weight(self) -> torch.Tensor:
         """bf16 image [N, 1, K] (= [N, K]) of the master weights, re-packed once per optimizer step."""
-        w = self.weight
-        key = self._key()
-        if self._pack is None or self._pack_key != key or self._pack.device != w.device:
-            if BATCH_PACKS[0] and getattr(self, _IS_REGISTERED, False):
-                _repack_stale(w.device)
-            else:
-                K, C = w.shape
-                self._pack = ops.conv2d_bf16_pack(w.detach().view(K, C, 1, 1),
-                                                  self._pack if self._pack is not None and self._pack.device == w.device else None)
-                self._pack_key = key
-                PACK_LAUNCHES[0] += 1
-        return self._pack
+        return weightimg.image(self._img or _slot(self, "_img"), self.weight)
 
     def packed_weight_t(self) -> torch.Tensor:
         """bf16 image [K, N] (the transposed weights the input-gradient GEMM reads)."""
-        w = self.weight
-        key = self._key()
-        if self._pack_t is None or self._pack_t_key != key or self._pack_t.device != w.device:
-            if BATCH_PACKS[0] and getattr(self, _IS_REGISTERED, False):
-                _repack_stale(w.device)
-            else:
-                self._pack_t = ops.pack_bf16(w.detach(), True,
-                                             self._pack_t if self._pack_t is not None and self._pack_t.device == w.device else None)
-                self._pack_t_key = key
-                PACK_LAUNCHES[0] += 1
-        return self._pack_t
+        return weightimg.image(self._img_t or _slot(self, "_img_t"), self.weight)
 
     def forward(self, x, addend=None):
         """`addend` (a tensor of the output's shape, e.g. the residual branch) is added in the kernel's epilogue."""
@@ -334,7 +284,8 @@ def use_salun_linears_bf16(model: nn.Module) -> int:
             if type(mod) is nn.Linear and mod.in_features % 32 == 0 and mod.out_features % 32 == 0 and \
                     ops.conv2d_bf16_supported(mod.in_features, mod.out_features, 1, 1, 0):
                 mod.__class__ = SalunLinearBF16
-                _register(mod)
+                _slot(mod, "_img", True)
+                _slot(mod, "_img_t", True)
                 n += 1
     return n
 
@@ -361,7 +312,7 @@ def use_salun_convs_bf16(model: nn.Module) -> int:
         R, s, p = mod.kernel_size[0], mod.stride[0], mod.padding[0]
         if C % 32 == 0 and K % 32 == 0 and ops.conv2d_bf16_supported(C, K, R, s, p):
             mod.__class__ = SalunConv2dBF16
-            _register(mod)
+            _slot(mod, "_img", True)
             n += 1
         else:
             mod.__class__ = _Fp32Island

@@ -13,25 +13,9 @@ import torch
 
 from .fastfn import FastFunction
 
-from . import _lib, ringpack
+from . import _lib, ringpack, weightimg
 from ._lib import c_double, c_int, c_int64, c_size_t, c_uint64, c_void_p, check
-
-
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-_cur_device = getattr(torch._C, "_cuda_getDevice", None)
-
-
-def _stream_handle(idx: Optional[int] = None) -> int:
-    """The raw handle of device `idx`'s (default: the current device's) current stream — what
-    `torch.cuda.current_stream(idx).cuda_stream` returns, without building a Stream object and re-probing the device on
-    each of ~4,500 calls per SD step."""
-    if _raw_stream is None or _cur_device is None:
-        return torch.cuda.current_stream(idx).cuda_stream
-    return _raw_stream(_cur_device() if idx is None else idx)
-
-
-def _stream() -> c_void_p:
-    return c_void_p(_stream_handle())
+from .streams import _stream, _stream_handle
 
 
 def _dev(t: Optional[torch.Tensor], dtype: torch.dtype, name: str, allow_none: bool = False) -> c_void_p:
@@ -87,10 +71,10 @@ def workspace(nbytes: int, device: torch.device, tag: str = "",
     return w
 
 
-# Bumped by every kernel that rewrites parameters through raw pointers (the fused optimizer steps, the proximal
-# step): torch's version counters do not see those writes, and derived images of the weights (the bf16 weight pack of
-# conv_bf16.py) are cached against this counter.
-PARAM_EPOCH = [0]
+# The parameter epoch and the pack counter of weightimg.py under the names tests and tools know: the same list objects.
+# Every kernel below that rewrites parameters through raw pointers calls weightimg.params_written().
+PARAM_EPOCH = weightimg.PARAM_EPOCH
+PACK_CALLS = weightimg.BF16_LAUNCHES
 
 
 # ----------------------------------------------------------------------------- K1
@@ -204,7 +188,7 @@ def masked_sgd_step(p: torch.Tensor, g: torch.Tensor, buf: Optional[torch.Tensor
                     lr: float, momentum: float, weight_decay: float, first_step: bool) -> None:
     n = p.numel()
     assert g.numel() == n and (buf is None or buf.numel() == n) and (m is None or m.numel() == n)
-    PARAM_EPOCH[0] += 1
+    weightimg.params_written()
     check(_lib.lib().salun_masked_sgd_step(_dev(p, torch.float32, "p"), _dev(g, torch.float32, "g"),
                                            _dev(buf, torch.float32, "buf", True), _dev(m, torch.uint8, "mask", True),
                                            c_double(lr), c_double(momentum), c_double(weight_decay),
@@ -229,7 +213,7 @@ def masked_adam_step(p: torch.Tensor, g: torch.Tensor, m1: torch.Tensor, v: torc
                      max_norm: float = 1.0, gscale: float = 1.0) -> None:
     n = p.numel()
     assert g.numel() == n and m1.numel() == n and v.numel() == n and (mask is None or mask.numel() == n)
-    PARAM_EPOCH[0] += 1
+    weightimg.params_written()
     check(_lib.lib().salun_masked_adam_step(_dev(p, torch.float32, "p"), _dev(g, torch.float32, "g"),
                                             _dev(m1, torch.float32, "exp_avg"), _dev(v, torch.float32, "exp_avg_sq"),
                                             _dev(mask, torch.uint8, "mask", True),
@@ -250,7 +234,7 @@ def masked_adam_step_coef(p, g, m1, v, mask, coef, beta1, beta2, eps, weight_dec
                           gscale=1.0) -> None:
     """masked_adam_step with the step-dependent scalars read from device memory (whole-step HIP graphs)."""
     n = p.numel()
-    PARAM_EPOCH[0] += 1
+    weightimg.params_written()
     check(_lib.lib().salun_masked_adam_step_coef(_dev(p, torch.float32, "p"), _dev(g, torch.float32, "g"),
                                                  _dev(m1, torch.float32, "exp_avg"), _dev(v, torch.float32, "exp_avg_sq"),
                                                  _dev(mask, torch.uint8, "mask", True),
@@ -353,16 +337,8 @@ def fim_square_accumulate(F: torch.Tensor, tmp: torch.Tensor, n_data: float) -> 
 
 
 # ----------------------------------------------------------------------------- K8
-_data_ws_cache: dict = {}
-
-
 def _data_ws_bytes(N: int, outC: int, outH: int, outW: int, R: int, conv_stride: int) -> int:
-    """salun_conv2d_data_workspace_bytes, remembered per shape (it is asked for every convolution call)."""
-    key = (N, outC, outH, outW, R, conv_stride)
-    v = _data_ws_cache.get(key)
-    if v is None:
-        v = _data_ws_cache[key] = int(_lib.lib().salun_conv2d_data_workspace_bytes(N, outC, outH, outW, R, conv_stride))
-    return v
+    return _q("salun_conv2d_data_workspace_bytes", N, outC, outH, outW, R, conv_stride)
 
 
 def conv2d_forward(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], stride: int, pad: int,
@@ -515,15 +491,9 @@ def conv2d_bf16_supported(C: int, K: int, R: int, stride: int, pad: int) -> bool
     return bool(_q("salun_conv2d_bf16_supported", C, K, R, stride, pad))
 
 
-# number of weight re-packs issued so far (SD/train_scripts.py::forget_and_target uses it to detect cold caches: a pack
-# kernel enqueued on one stream while another stream is about to read the same image)
-PACK_CALLS = [0]
-
-
 def conv2d_bf16_pack(w: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """fp32 OIHW master weights -> the bf16 image [K, R*R, C] the forward and backward-data kernels read."""
     K, C, R, _ = w.shape
-    PACK_CALLS[0] += 1
     if out is None:
         out = torch.empty((K, R * R, C), dtype=torch.bfloat16, device=w.device)
     check(_lib.lib().salun_conv2d_bf16_pack_weights(_dev(w, torch.float32, "w"), _dev(out, torch.bfloat16, "wp"), K, C, R,
@@ -538,7 +508,6 @@ def bf16_pack_batch(jobs) -> int:
     jobs = list(jobs)
     if not jobs:
         return 0
-    PACK_CALLS[0] += 1
     L, st, cap = _lib.lib(), _stream(), _lib.SALUN_BF16_PACK_MAX_JOBS
     launches = 0
     for i in range(0, len(jobs), cap):
@@ -672,7 +641,6 @@ def gemm_bf16_tn(dy: torch.Tensor, x: torch.Tensor, out: Optional[torch.Tensor] 
 def pack_bf16(w: torch.Tensor, transposed: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """fp32 [N, K] master weights -> bf16 [N, K] (or [K, N] with `transposed`): the images gemm_bf16_nt reads."""
     N, K = w.shape
-    PACK_CALLS[0] += 1
     if out is None:
         out = torch.empty((K, N) if transposed else (N, K), dtype=torch.bfloat16, device=w.device)
     check(_lib.lib().salun_pack_bf16(_dev(w, torch.float32, "w"), _dev(out, torch.bfloat16, "wp"), N, K, int(bool(transposed)),
@@ -958,7 +926,7 @@ def proximal_step(p: torch.Tensor, p0: torch.Tensor, ratio: int, scratch: Option
                   scratch_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """In place soft-threshold of `p` towards `p0` with threshold = the ratio-th smallest |p - p0|
     (RL_pro.py:52-60).  Returns the threshold as a 1-element device tensor (no host sync)."""
-    PARAM_EPOCH[0] += 1
+    weightimg.params_written()
     n = p.numel()
     if ratio < 1:
         raise IndexError("index -1 is out of bounds for dimension 0 with size 0")  # reference: topk(.., 0)[0][-1]

@@ -11,7 +11,7 @@ from typing import Optional, Sequence
 
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, weightimg
 from ._lib import c_double, c_int64, c_uint64, check
 from .ops import _dev, _stream
 
@@ -121,7 +121,7 @@ def apply(p: torch.Tensor, F: torch.Tensor, shapes: Sequence[torch.Size], num_cl
     if nbatches < 1:
         raise ValueError("fisher_new needs at least one batch")
     tab = torch.tensor(rows, dtype=torch.int64).reshape(-1).to(p.device)
-    ops.PARAM_EPOCH[0] += 1  # a raw-pointer write of the parameters: derived weight images are stale
+    weightimg.params_written()  # a raw-pointer write of the parameters: derived weight images are stale
     check(_lib.lib().salun_ff_apply(_dev(p, torch.float32, "p"), _dev(F, torch.float32, "F"),
                                     _dev(tab, torch.int64, "table"), len(rows), c_int64(tiles), c_double(nbatches),
                                     c_double(alpha), c_uint64(seed), _stream()), "salun_ff_apply")

@@ -10,7 +10,7 @@ from typing import Optional
 
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, weightimg
 from ._lib import c_double, c_int64, check
 from .ops import _dev, _stream
 
@@ -95,7 +95,7 @@ def apply(p: torch.Tensor, v: torch.Tensor, g0: torch.Tensor, beta: torch.Tensor
     n = p.numel()
     if v.numel() != n or g0.numel() != n or (mask is not None and mask.numel() != n):
         raise ValueError("p, v, g0 and mask must have the same length")
-    ops.PARAM_EPOCH[0] += 1  # a raw-pointer write of the parameters: derived weight images are stale
+    weightimg.params_written()  # a raw-pointer write of the parameters: derived weight images are stale
     check(_lib.lib().salun_iu_apply(_dev(p, torch.float32, "p"), _dev(v, torch.float32, "v"),
                                     _dev(g0, torch.float32, "g0"), _dev(beta, torch.float64, "beta"),
                                     _dev(mask, torch.uint8, "mask", True), c_double(alpha), c_int64(n), _stream()),

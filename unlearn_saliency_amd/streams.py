@@ -17,9 +17,28 @@ backward pass (empty shard) must not leave the others waiting in one.  ~10 - 100
 """
 from __future__ import annotations
 
+import ctypes
 import os
+from typing import Optional
 
 import torch
+
+_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+_cur_device = getattr(torch._C, "_cuda_getDevice", None)
+
+
+def _stream_handle(idx: Optional[int] = None) -> int:
+    """The raw handle of device `idx`'s (default: the current device's) current stream — what
+    `torch.cuda.current_stream(idx).cuda_stream` returns, without building a Stream object and re-probing the device on
+    each of ~4,500 calls per SD step.  (ops.py hands it to every kernel; weightimg.py remembers which stream packed.)"""
+    if _raw_stream is None or _cur_device is None:
+        return torch.cuda.current_stream(idx).cuda_stream
+    return _raw_stream(_cur_device() if idx is None else idx)
+
+
+def _stream() -> ctypes.c_void_p:
+    return ctypes.c_void_p(_stream_handle())
+
 
 _PROBE = os.environ.get("SALUN_STREAM_PROBE", "1") != "0"
 _keep: list = []   # rejected candidates stay alive: torch hands streams out of a pool, a freed one would come back

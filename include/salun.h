@@ -722,6 +722,48 @@ int salun_fill_normal(float *out /*dev*/, int64_t n, uint64_t seed, double mean,
                       salun_stream_t stream);
 int salun_fill_u8(uint8_t *out /*dev*/, int64_t n, uint64_t seed, salun_stream_t stream);
 
+/* ----------------------------------------------------------------- K19 --
+ * Sampling an (unlearned) CFG-DDPM (DDPM/sample.py).
+ *
+ * salun_sampler_step: one reverse step x_t -> x_next over a batch of B images of chw floats, fp32, one launch.
+ *   e      = (1 + cond_scale) * eps_cond - cond_scale * eps_null        (eps_null NULL: e = eps_cond)
+ *   at, an = abar[idx_t], abar[idx_next]   (the device table of alpha_bar_table: entry t + 1 is abar_t, entry 0 is 1;
+ *            1 <= idx_t < table_len, 0 <= idx_next < table_len)
+ *   SALUN_SAMPLER_ANCESTRAL:   beta = 1 - at / an;  x0 = clamp(sqrt(1 / at) x_t - sqrt(1 / at - 1) e, -1, 1);
+ *            x_next = (sqrt(an) beta x0 + sqrt(1 - beta) (1 - an) x_t) / (1 - at) + sqrt(beta) z, no z at idx_t == 1
+ *   SALUN_SAMPLER_GENERALIZED: x0 = (x_t - sqrt(1 - at) e) / sqrt(at);  c1 = eta sqrt((1 - at / an)(1 - an) / (1 - at));
+ *            x_next = sqrt(an) x0 + c1 z + sqrt(1 - an - c1^2) e
+ * with the coefficients computed on the device in the operation order of DDPM/functions/denoising.py.  z is `noise`
+ * (dev, B * chw) when given; otherwise row b draws the counter-based normal of salun_fill_normal at element e of the
+ * stream keyed by (seed, step, image_ids[b]) — the values salun_sampler_noise writes — so no noise tensor is read and
+ * an image does not depend on the batch it is sampled in.  x0 (optional) receives the x0 estimate; x_next may be x_t. */
+#define SALUN_SAMPLER_ANCESTRAL 0
+#define SALUN_SAMPLER_GENERALIZED 1
+int salun_sampler_step(const float *x_t /*dev*/, const float *eps_cond /*dev*/, const float *eps_null /*dev or NULL*/,
+                       double cond_scale, const float *abar /*dev*/, int table_len, int idx_t, int idx_next, int variant,
+                       double eta, const float *noise /*dev or NULL*/, uint64_t seed,
+                       const int64_t *image_ids /*dev, B; may be NULL with noise*/, int64_t step, float *x_next /*dev*/,
+                       float *x0 /*dev or NULL*/, int64_t B, int64_t chw, salun_stream_t stream);
+
+/* out[b * chw + e] = salun_fill_normal(key(seed, step, image_ids[b]), 0, 1)[e] with
+ * key = splitmix64(splitmix64(splitmix64(seed) + step) + image id): the start noise x_T (step 0) and, for tests, the
+ * noise salun_sampler_step draws at a step. */
+int salun_sampler_noise(float *out /*dev*/, uint64_t seed, const int64_t *image_ids /*dev, B*/, int64_t step, int64_t B,
+                        int64_t chw, salun_stream_t stream);
+
+/* lohi[0] = min x, lohi[1] = max x over n >= 1 floats: per-workgroup partials, then one workgroup, in a fixed order
+ * (no float atomics). */
+size_t salun_minmax_workspace_bytes(int64_t n);
+int salun_minmax(const float *x /*dev*/, int64_t n, float *lohi /*dev, 2*/, void *ws /*dev*/, size_t ws_bytes,
+                 salun_stream_t stream);
+
+/* B images (C, HW) fp32 in the model's range -> uint8 (HW, C), one workgroup per image, C * HW <= 16000:
+ *   v = clamp(rescaled ? (x + 1) / 2 : x, 0, 1);  u8 = trunc(clamp((clamp(v, lo, hi) - lo) / max(hi - lo, 1e-5) * 255 + 0.5, 0, 255))
+ * `range` NULL: lo / hi are the image's own min / max of v.  Otherwise range[0..1] (dev) is a min / max of x values
+ * (salun_minmax over all images of a grid), mapped like the pixels. */
+int salun_images_to_u8(const float *x /*dev*/, uint8_t *out /*dev*/, int64_t B, int C, int HW, int rescaled,
+                       const float *range /*dev, 2, or NULL*/, salun_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -78,3 +78,36 @@ def cycle(dl):
     while True:
         for data in dl:
             yield data
+
+
+def create_class_labels(string: str, n_classes: int = 10):
+    """`--classes_to_generate` (reference functions/__init__.py:126-133): a comma list of class ids, or — as soon as
+    one entry starts with "x" — every class except the "xN" entries (plain ids next to them are ignored, as there).
+    -> (classes, excluded)."""
+    entries = string.split(",")
+    excluded = [int(e[1:]) for e in entries if e.startswith("x")]
+    if excluded:
+        return [k for k in range(n_classes) if k not in excluded], excluded
+    return [int(e) for e in entries], []
+
+
+def rank_image_ids(first: int, count: int, rank: int = 0, world_size: int = 1):
+    """The image ids of [first, first + count) that `rank` samples: dealt round-robin over the GLOBAL id
+    (id % world_size == rank), so every id belongs to exactly one rank whatever the class or round it falls into."""
+    if not 0 <= rank < world_size:
+        raise ValueError(f"rank {rank} outside a world of {world_size}")
+    return [i for i in range(first, first + count) if i % world_size == rank]
+
+
+def sampling_rounds(ids, batch_size: int):
+    """The reference's rounds over `sampling.batch_size` (runners/diffusion.py:690-704): full batches, then the ragged
+    tail.  -> list of id lists."""
+    ids = list(ids)
+    n_rounds = len(ids) // batch_size + (0 if len(ids) % batch_size == 0 else 1)
+    out, n_left = [], len(ids)
+    for _ in range(n_rounds):
+        n = batch_size if n_left >= batch_size else n_left
+        done = len(ids) - n_left
+        out.append(ids[done:done + n])
+        n_left -= n
+    return out

@@ -76,3 +76,38 @@ def generalized_steps_conditional(x, c, seq, model, b, cond_scale=3.0, keep: str
 
 def ddpm_step_conditional(x, c, seq, model, b, cond_scale, keep: str = "all", **kwargs):
     return _loop(x, seq, lambda xt, t: model(xt, t.float(), c, cond_scale=cond_scale, mode="test"), b, True, 0.0, keep)
+
+
+def fused_steps_conditional(x, c, image_ids, seq, model, betas, cond_scale, variant, eta, seed, noise=None,
+                            keep: str = "last"):
+    """The loop of `_loop` for the conditional samplers on the fused step kernel (K19, ops_sampler.sampler_step): per
+    step the model gives its two raw predictions (`model.eps_pair`; only the conditional one when `cond_scale == 0`) and
+    ONE launch does the guidance combine, the x0 estimate, the update and the noise term, with the coefficients taken
+    from the device alpha-bar table inside the kernel.  `variant`: "ddpm_noisy" / "ancestral" or "generalized" (with
+    `eta`).  The step noise is keyed by (seed, step, image_ids[row]), so no noise tensor exists and an image does not
+    depend on its batch; `noise` (a sequence of one tensor per step) replaces it for parity tests.  Device tensors only.
+    Returns (xs, x0s) like `_loop`: device tensors of the last step (`keep="last"`) or the whole trajectory, x first."""
+    from ... import ops_sampler
+    seq = list(seq)
+    prev = [-1] + seq[:-1]
+    kind = ops_sampler.VARIANTS[variant] if isinstance(variant, str) else int(variant)
+    abar = alpha_bar_table(betas.to(x.device)).contiguous()
+    n = x.size(0)
+    t = torch.empty(n, device=x.device)
+    xs, x0s = [x], []
+    cur, x0 = x, torch.empty_like(x)
+    with torch.no_grad():
+        for k, (i, j) in enumerate(zip(reversed(seq), reversed(prev))):
+            t.fill_(float(i))
+            ec, en = model.eps_pair(cur, t, c, null=cond_scale != 0)
+            # the caller's x is not written: the first step gets a new tensor, later ones run in place
+            fresh = cur is x or keep == "all"
+            if keep == "all":
+                x0 = torch.empty_like(x)
+            cur = ops_sampler.sampler_step(cur, ec, en, cond_scale, abar, i + 1, j + 1, kind, eta,
+                                           noise=None if noise is None else noise[k], seed=seed, image_ids=image_ids,
+                                           step=ops_sampler.START_STEP + 1 + k, out=None if fresh else cur, x0=x0)
+            if keep == "all":
+                xs.append(cur)
+                x0s.append(x0)
+    return (xs, x0s) if keep == "all" else ([cur], [x0])

@@ -246,6 +246,11 @@ class Conditional_Model(nn.Module):
         null_logits = self._forward(x, t, c, cond_drop_prob=1.0)
         return (1 + cond_scale) * logits - cond_scale * null_logits
 
+    def eps_pair(self, x, t, c, null=True):
+        """The two raw predictions of classifier-free guidance, (eps(x, c), eps(x, ∅)), uncombined: the fused sampler
+        step does the combine itself (functions/denoising.py:fused_steps_conditional).  `null=False`: (eps(x, c), None)."""
+        return self._forward(x, t, c, cond_drop_prob=0.0), (self._forward(x, t, c, cond_drop_prob=1.0) if null else None)
+
     def _projections(self, emb_act):
         """Every ResnetBlock adds Linear(emb_act) of the SAME activation (reference models/diffusion.py:120): with the
         own GEMM all 22 are one grouped launch (and one / one / 22-in-one in backward) instead of 22 library GEMMs with

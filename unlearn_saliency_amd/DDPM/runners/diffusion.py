@@ -6,8 +6,9 @@
 
 — same constructor (`Diffusion(args, config)`), same `args` / YAML fields, same artefacts
 (`results/cifar10/mask/{label}/with_0.5.pt` with `module.`-prefixed int64 tensors; `ckpts/ckpt.pth` =
-`[model_state, optimizer_state, step]`; `fisher_dict.pkl`).  Sampling / pre-training / FID stay out of
-scope.
+`[model_state, optimizer_state, step]`; `fisher_dict.pkl`).  `sample()` and its modes (reference :621-931) write
+the folders of PNGs the evaluation and `save_fim` / `train_forget` read.  Pre-training / FID stay
+out of scope.
 
 What is different underneath (MI355X-first):
   * one process per GPU + RCCL instead of nn.DataParallel's per-step parameter broadcast / output gather;
@@ -342,12 +343,16 @@ class Diffusion(object):
         return helper
 
     # ------------------------------------------------------------------ sampling (evaluation of an unlearned model)
-    def sample_image(self, x, model, c, cond_scale, last=True):
+    def sample_image(self, x, model, c, cond_scale, last=True, fused=False, image_ids=None):
         """Reverse process from noise `x` for classes `c` (reference :828-875): `args.sample_type` "generalized" (DDIM,
         `args.eta`) or "ddpm_noisy" (ancestral), `args.skip_type` "uniform" | "quad", `args.timesteps` steps.
         (The reference's "ddpm_noisy" branch imports a misspelt name, `ddpm_steps_conditional`, and fails; here it
-        runs `ddpm_step_conditional`.)  `last=True` keeps only the final state on the device."""
-        from ..functions.denoising import ddpm_step_conditional, generalized_steps_conditional
+        runs `ddpm_step_conditional`.)  `last=True` keeps only the final state on the device.
+        `fused=True`: the same loop on the fused step kernel (functions/denoising.py:fused_steps_conditional), its
+        noise keyed by (`args.seed`, step, `image_ids`) — the global ids of the rows of `x` — instead of torch's
+        generator."""
+        from ..functions.denoising import (ddpm_step_conditional, fused_steps_conditional,
+                                           generalized_steps_conditional)
         args = self.args
         if args.skip_type == "uniform":
             seq = range(0, self.num_timesteps, self.num_timesteps // args.timesteps)
@@ -356,13 +361,149 @@ class Diffusion(object):
         else:
             raise NotImplementedError
         keep = "last" if last else "all"
-        if args.sample_type == "generalized":
+        if fused:
+            if args.sample_type not in ("generalized", "ddpm_noisy"):
+                raise NotImplementedError
+            if image_ids is None:
+                raise ValueError("sample_image(fused=True) needs the rows' global image ids")
+            out = fused_steps_conditional(x, c, image_ids, seq, model, self.betas, cond_scale, args.sample_type,
+                                          args.eta, args.seed, keep=keep)
+        elif args.sample_type == "generalized":
             out = generalized_steps_conditional(x, c, seq, model, self.betas, cond_scale, eta=args.eta, keep=keep)
         elif args.sample_type == "ddpm_noisy":
             out = ddpm_step_conditional(x, c, seq, model, self.betas, cond_scale, keep=keep)
         else:
             raise NotImplementedError
         return out[0][-1] if last else out
+
+    # ------------------------------------------------------------------ sample.py: folders of PNGs (reference :621-931)
+    def load_ema_model(self):
+        """(model, test_model) from `{ckpt_folder}/ckpts/ckpt.pth` (`_load_model`: keys with or without `module.`,
+        `args.synthetic` without a checkpoint), both in eval mode; `test_model` is the EMA copy (states[-1]) when
+        `config.model.ema` is set, else the model itself (reference :621-662)."""
+        model = self._load_model()
+        test_model = model
+        if getattr(self.config.model, "ema", False):
+            helper = self._ema(model)
+            path = os.path.join(self.args.ckpt_folder, "ckpts/ckpt.pth") if getattr(self.args, "ckpt_folder", None) else None
+            if path and os.path.exists(path):
+                states = torch.load(path, map_location=self.device, weights_only=False)
+                helper.load_state_dict(strip_prefix(states[-1]))
+            test_model = helper.ema_copy(model)
+            if not getattr(self.args, "library_conv", False):
+                from ...conv import use_salun_convs
+                use_salun_convs(test_model)
+            test_model.eval()
+        model.eval()
+        return model, test_model
+
+    def sample(self):
+        """`sample.py`: dispatch on `args.mode` (reference :642-671; its visualization samples the raw model, named by
+        the guidance scale)."""
+        model, test_model = self.load_ema_model()
+        mode = self.args.mode
+        if mode == "sample_fid":
+            self.sample_fid(test_model, self.args.cond_scale)
+        elif mode == "sample_classes":
+            self.sample_classes(test_model, self.args.cond_scale)
+        elif mode == "visualization":
+            self.sample_visualization(model, str(self.args.cond_scale), self.args.cond_scale)
+        else:
+            raise ValueError(f"unknown --mode {mode!r} (sample_fid | sample_classes | visualization)")
+
+    def _sample_round(self, model, ids, labels, cond_scale):
+        """One round: images with the global ids `ids` and classes `labels` -> final states (n, C, H, W) on the device.
+        The start noise is the keyed normal of step 0, the steps draw on (args.seed, step, id) (fused=True)."""
+        from ... import ops_sampler
+        d = self.config.data
+        image_ids = torch.tensor(list(ids), dtype=torch.int64).to(self.device)
+        c = torch.tensor([int(v) for v in labels], dtype=torch.int64).to(self.device)
+        x = ops_sampler.sampler_noise(image_ids, (d.channels, d.image_size, d.image_size), self.args.seed)
+        return self.sample_image(x, model, c, cond_scale, fused=True, image_ids=image_ids)
+
+    def _to_u8(self, x, value_range=None):
+        """Device (n, C, H, W) states -> host uint8 (n, H, W, C) in ONE copy: `inverse_data_transform` and the
+        min-max normalisation of `save_image(normalize=True)` happen in `salun_images_to_u8`."""
+        from ... import ops_sampler
+        d = self.config.data
+        if hasattr(self.config, "image_mean") or getattr(d, "logit_transform", False):
+            raise NotImplementedError("sampling: image_mean / logit_transform configs are outside the u8 kernel's map")
+        return ops_sampler.images_to_u8(x, rescaled=bool(d.rescaled), value_range=value_range).cpu().numpy()
+
+    def _sample_to_files(self, model, cond_scale, classes, n_per_class, path_of):
+        """The reference's loop over classes and rounds (:688-725): image ids run on across the classes and name the
+        files; the ids are dealt over ranks by `rank_image_ids`, each rank's share of a class goes in rounds of
+        `sampling.batch_size` with a ragged tail."""
+        from ..functions import rank_image_ids, sampling_rounds
+        from .. import pngio
+        bs = self.config.sampling.batch_size
+        written = 0
+        with torch.no_grad():
+            for k, cl in enumerate(classes):
+                ids = rank_image_ids(k * n_per_class, n_per_class, sdist.rank(), sdist.world_size())
+                for chunk in sampling_rounds(ids, bs):
+                    u8 = self._to_u8(self._sample_round(model, chunk, [cl] * len(chunk), cond_scale))
+                    for img, img_id in zip(u8, chunk):
+                        pngio.write_png(path_of(cl, img_id), img)
+                    written += len(chunk)
+        return written
+
+    def sample_classes(self, model, cond_scale):
+        """`class_samples/<class>/<id>.png` for every class of `--classes_to_generate`: the dataset `save_fim` and
+        `train_forget` read back, and the classifier evaluation's input (reference :673-725)."""
+        from ..functions import create_class_labels
+        args = self.args
+        sample_dir = os.path.join(args.ckpt_folder, "class_samples")
+        classes, _ = create_class_labels(args.classes_to_generate, n_classes=self.config.data.n_classes)
+        for cl in classes:
+            os.makedirs(os.path.join(sample_dir, str(cl)), exist_ok=True)
+        return self._sample_to_files(model, cond_scale, classes, args.n_samples_per_class,
+                                     lambda cl, i: os.path.join(sample_dir, str(cl), f"{i}.png"))
+
+    def sample_one_class(self, model, cond_scale, class_label, total_n_samples=500):
+        """`class_<label>/<id>.png`, 500 images of one class (reference :727-771)."""
+        sample_dir = os.path.join(self.args.ckpt_folder, "class_" + str(class_label))
+        os.makedirs(sample_dir, exist_ok=True)
+        return self._sample_to_files(model, cond_scale, [int(class_label)], total_n_samples,
+                                     lambda cl, i: os.path.join(sample_dir, f"{i}.png"))
+
+    def sample_fid(self, model, cond_scale):
+        """`fid_samples_guidance_<s>[_excluded_class_a_b]/<id>.png`, all classes in one folder (reference :773-826)."""
+        from ..functions import create_class_labels
+        args = self.args
+        classes, excluded = create_class_labels(args.classes_to_generate, n_classes=self.config.data.n_classes)
+        sample_dir = f"fid_samples_guidance_{args.cond_scale}"
+        if excluded:
+            sample_dir = f"{sample_dir}_excluded_class_{'_'.join(str(i) for i in excluded)}"
+        sample_dir = os.path.join(args.ckpt_folder, sample_dir)
+        os.makedirs(sample_dir, exist_ok=True)
+        return self._sample_to_files(model, cond_scale, classes, args.n_samples_per_class,
+                                     lambda cl, i: os.path.join(sample_dir, f"{i}.png"))
+
+    def sample_visualization(self, model, name, cond_scale):
+        """`sample-<name>.png`: `training.visualization_samples` images, one row per class, no padding, normalised over
+        the whole grid (reference :877-931; written to `config.log_dir` when the run has one, else `ckpt_folder`)."""
+        from ... import ops_sampler
+        from .. import pngio
+        config = self.config
+        total = config.training.visualization_samples
+        n_classes = config.data.n_classes
+        assert total % n_classes == 0
+        per_class = total // n_classes
+        bs = config.sampling.batch_size
+        n_rounds = total // bs if bs < total else 1
+        labels = torch.repeat_interleave(torch.arange(n_classes), per_class)
+        ids = torch.arange(total)
+        with torch.no_grad():
+            xs = [self._sample_round(model, i.tolist(), c.tolist(), cond_scale)
+                  for i, c in zip(torch.chunk(ids, n_rounds, dim=0), torch.chunk(labels, n_rounds, dim=0))]
+            x = torch.cat(xs) if len(xs) > 1 else xs[0]
+            u8 = self._to_u8(x, value_range=ops_sampler.minmax(x))
+        out_dir = getattr(config, "log_dir", None) or self.args.ckpt_folder
+        path = os.path.join(out_dir, f"sample-{name}.png")
+        if sdist.rank() == 0:
+            pngio.write_png(path, pngio.image_grid(u8, per_class))
+        return path
 
     # ---------------------------------------------- EWC / Selective Amnesia (SURVEY.md §8 F3)
     def forget_step(self, model, optimizer, remember_batch, fisher_flat, params_mle_flat):

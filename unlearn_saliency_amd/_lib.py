@@ -175,6 +175,13 @@ SIGNATURES = {
     "salun_fill_uniform": (c_int, [c_void_p, c_int64, c_uint64, c_double, c_double, c_void_p]),
     "salun_fill_normal": (c_int, [c_void_p, c_int64, c_uint64, c_double, c_double, c_void_p]),
     "salun_fill_u8": (c_int, [c_void_p, c_int64, c_uint64, c_void_p]),
+    "salun_sampler_step": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_int, c_int, c_int, c_int,
+                                   c_double, c_void_p, c_uint64, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                   c_int64, c_void_p]),
+    "salun_sampler_noise": (c_int, [c_void_p, c_uint64, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
+    "salun_minmax_workspace_bytes": (c_size_t, [c_int64]),
+    "salun_minmax": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "salun_images_to_u8": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -1,0 +1,97 @@
+"""Tensor-level wrappers of the sampler kernels (K19, csrc/salun_sampler.hip; include/salun.h).
+
+Same conventions as ops.py / ops_ff.py: device tensors only, raw pointers and the current stream handed to
+libsalun.so, a failing call raises `SalunError`.  Images are (B, C, H, W) fp32 in the model's range; `image_ids` is a
+(B,) int64 device vector of GLOBAL image ids: every draw is keyed by (seed, step, image id), never by the batch.
+"""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import torch
+
+from . import _lib, ops
+from ._lib import c_double, c_int64, c_size_t, c_uint64, check
+from .draws import _M64, _splitmix64
+from .ops import _dev, _stream
+
+ANCESTRAL, GENERALIZED = 0, 1  # SALUN_SAMPLER_ANCESTRAL / SALUN_SAMPLER_GENERALIZED
+VARIANTS = {"ancestral": ANCESTRAL, "ddpm_noisy": ANCESTRAL, "generalized": GENERALIZED}
+START_STEP = 0  # the step index of the start noise x_T; reverse step k (0-based, in the order it is taken) draws at k + 1
+IMAGES_U8_MAX_CHW = 16000
+
+
+def sampler_key(seed: int, step: int, image_id: int) -> int:
+    """The `salun_fill_normal` seed of one image's noise at one step (the kernels derive the same key on the device)."""
+    return _splitmix64((_splitmix64((_splitmix64(int(seed) & _M64) + int(step)) & _M64) + int(image_id)) & _M64)
+
+
+def _rows(t: torch.Tensor) -> Tuple[int, int]:
+    if t.dim() < 1:
+        raise ValueError("expected a batch of images")
+    B = t.shape[0]
+    return B, (t.numel() // B if B else 0)
+
+
+def sampler_noise(image_ids: torch.Tensor, shape, seed: int, step: int = START_STEP) -> torch.Tensor:
+    """(B, *shape) fp32: row b is fill_normal(prod(shape), sampler_key(seed, step, image_ids[b]))."""
+    B = image_ids.numel()
+    out = torch.empty((B,) + tuple(shape), dtype=torch.float32, device=image_ids.device)
+    check(_lib.lib().salun_sampler_noise(_dev(out, torch.float32, "out"), c_uint64(int(seed) & _M64),
+                                         _dev(image_ids, torch.int64, "image_ids"), c_int64(step), c_int64(B),
+                                         c_int64(_rows(out)[1]), _stream()), "salun_sampler_noise")
+    return out
+
+
+def sampler_step(x: torch.Tensor, eps_cond: torch.Tensor, eps_null: Optional[torch.Tensor], cond_scale: float,
+                 abar: torch.Tensor, idx_t: int, idx_next: int, variant: int, eta: float = 0.0,
+                 noise: Optional[torch.Tensor] = None, seed: int = 0, image_ids: Optional[torch.Tensor] = None,
+                 step: int = 0, out: Optional[torch.Tensor] = None, x0: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One reverse step (see salun_sampler_step).  `abar`: the device table of `alpha_bar_table`; `idx_t` / `idx_next`
+    are i + 1 / j + 1 of the loop.  `noise` given: used as the step's z; else drawn on (seed, step, image_ids).
+    `out` defaults to a new tensor (pass `x` for in place); `x0`, when given, receives the x0 estimate."""
+    B, chw = _rows(x)
+    if out is None:
+        out = torch.empty_like(x)
+    for nm, t in (("eps_cond", eps_cond), ("eps_null", eps_null), ("noise", noise), ("out", out), ("x0", x0)):
+        if t is not None and t.shape != x.shape:
+            raise ValueError(f"{nm} {tuple(t.shape)} does not match x {tuple(x.shape)}")
+    if image_ids is not None and image_ids.numel() != B:
+        raise ValueError(f"image_ids has {image_ids.numel()} entries for a batch of {B}")
+    f = lambda t, nm: _dev(t, torch.float32, nm, True)
+    check(_lib.lib().salun_sampler_step(_dev(x, torch.float32, "x"), _dev(eps_cond, torch.float32, "eps_cond"),
+                                        f(eps_null, "eps_null"), c_double(cond_scale), _dev(abar, torch.float32, "abar"),
+                                        abar.numel(), int(idx_t), int(idx_next), int(variant), c_double(eta),
+                                        f(noise, "noise"), c_uint64(int(seed) & _M64),
+                                        _dev(image_ids, torch.int64, "image_ids", True), c_int64(step),
+                                        _dev(out, torch.float32, "out"), f(x0, "x0"), c_int64(B), c_int64(chw),
+                                        _stream()), "salun_sampler_step")
+    return out
+
+
+def minmax(x: torch.Tensor) -> torch.Tensor:
+    """Device tensor [min x, max x] (fixed reduction order)."""
+    L = _lib.lib()
+    n = x.numel()
+    nbytes = int(L.salun_minmax_workspace_bytes(c_int64(n)))
+    ws = ops.workspace(nbytes, x.device)
+    lohi = torch.empty(2, dtype=torch.float32, device=x.device)
+    check(L.salun_minmax(_dev(x, torch.float32, "x"), c_int64(n), _dev(lohi, torch.float32, "lohi"),
+                         _dev(ws, torch.uint8, "ws"), c_size_t(nbytes), _stream()), "salun_minmax")
+    return lohi
+
+
+def images_to_u8(x: torch.Tensor, rescaled: bool = True, value_range: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(B, C, H, W) fp32 in the model's range -> (B, H, W, C) uint8: the reference's `inverse_data_transform` followed
+    by torchvision's `save_image(normalize=True)`, per image, or over `value_range` = `minmax(x)` of a whole grid."""
+    if x.dim() != 4:
+        raise ValueError(f"x {tuple(x.shape)} must be (B, C, H, W)")
+    B, C, H, W = x.shape
+    if C * H * W > IMAGES_U8_MAX_CHW:
+        raise NotImplementedError(f"images_to_u8: an image of {C}x{H}x{W} floats does not fit the workgroup's LDS "
+                                  f"({IMAGES_U8_MAX_CHW} floats)")
+    out = torch.empty((B, H, W, C), dtype=torch.uint8, device=x.device)
+    check(_lib.lib().salun_images_to_u8(_dev(x, torch.float32, "x"), _dev(out, torch.uint8, "out"), c_int64(B), C,
+                                        H * W, 1 if rescaled else 0, _dev(value_range, torch.float32, "value_range", True),
+                                        _stream()), "salun_images_to_u8")
+    return out

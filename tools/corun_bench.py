@@ -1,6 +1,6 @@
 """What a memory-bound kernel pays for sharing the chip with a backward-weight kernel: BatchNorm backward (partial +
 apply, layer-1 shape of ResNet-18 at batch 256) timed alone and while a second stream loops backward-weight launches.
-Run under SALUN_LIB=<A/B build> to compare backward-weight kernels."""
+Run under SALUN_LIB=<other build> (e.g. a `tools/lab_build.sh rev` build) to compare backward-weight kernels."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

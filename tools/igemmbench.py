@@ -1,5 +1,5 @@
-"""Forward / backward-data only, three ResNet-18 shapes (batch 256), 30 calls each; with SALUN_LIB=<A/B build>
-(csrc/salun_conv.hip: SALUN_IGEMM_EXP) it shows where conv_igemm's time goes."""
+"""Forward / backward-data only, three ResNet-18 shapes (batch 256), 30 calls each; SALUN_LIB=<other build> (e.g. a
+`tools/lab_build.sh rev` build of another revision) times that library instead."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

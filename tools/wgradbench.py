@@ -1,6 +1,6 @@
 """Backward-weight only, three ResNet-18 shapes (batch 256): mean time of `ops.conv2d_backward_weight`
-(conv_wgrad + conv_wgrad_reduce) over 30 calls.  Used with SALUN_LIB=<A/B build> (csrc/salun_conv.hip:
-SALUN_WGRAD_EXP) to see where the kernel's time goes; prints one line per shape."""
+(conv_wgrad + conv_wgrad_reduce) over 30 calls; prints one line per shape.  SALUN_LIB=<other build> (e.g. a
+`tools/lab_build.sh rev` build of another revision) times that library instead."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -85,17 +85,11 @@ class Downsample(nn.Module):
         return self.op(x)
 
 
-import os as _os
-_EMB_FP32 = _os.environ.get("SALUN_SD_EMB_FP32", "1") != "0"   # A/B switch: 0 = Linear(SiLU(emb)) under autocast per block
-
-
 def _emb_term(lin, emb):
     """`emb_layers(emb)` = Linear(SiLU(emb)) of a ResBlock for the bf16 kernels, whose epilogue takes it in fp32: computed in
     fp32 outside autocast — 8 rows; under autocast every call cast the fp32 weight, the bias and the result (three copy
     launches around a 3 us product, x 113 calls per SD step) — from ONE SiLU(emb) per U-Net pass (`UNetModel.forward`
     leaves it on the tensor; the 22 ResBlocks of a pass and their checkpoint recomputes share it)."""
-    if not _EMB_FP32:
-        return lin(F.silu(emb)).float()
     with torch.autocast("cuda", enabled=False):
         act = getattr(emb, "_salun_silu", None)
         if act is None:
@@ -314,7 +308,7 @@ class UNetModel(nn.Module):
 
     def forward(self, x, timesteps=None, context=None, y=None, **kwargs):
         emb = self.time_embed(timestep_embedding(timesteps, self.model_channels).to(self.time_embed[0].weight.dtype))
-        if _EMB_FP32 and emb.is_cuda and isinstance(self.middle_block[0].in_layers[2], SalunConv2dBF16):
+        if emb.is_cuda and isinstance(self.middle_block[0].in_layers[2], SalunConv2dBF16):
             with torch.autocast("cuda", enabled=False):
                 emb._salun_silu = F.silu(emb.float())  # shared by every ResBlock of this pass (_emb_term)
         hs, h = [], x

@@ -27,14 +27,8 @@ LIBRARY_CONV_CALLS = {"shape": 0, "dtype_or_autocast": 0, "backward": 0}
 _STRICT = [False]
 
 
-# SALUN_BLOCK_NODES=0: keep the diffusion ResnetBlocks as separate autograd nodes (A/B switch for the benchmarks)
-_BLOCK_NODES = [os.environ.get("SALUN_BLOCK_NODES", "1") != "0"]
 # SALUN_OWN_GEMM=0: keep the diffusion U-Nets' Linear layers and fp32 attention on the library (A/B switch)
 _OWN_GEMM = [os.environ.get("SALUN_OWN_GEMM", "1") != "0"]
-
-
-# SALUN_RING=0: keep every 3x3 convolution on conv_igemm (A/B switch for the benchmarks)
-_RING = [os.environ.get("SALUN_RING", "1") != "0"]
 
 
 def strict(on: bool = True) -> None:
@@ -152,17 +146,14 @@ def use_salun_convs(model: nn.Module) -> int:
             continue
     for mod in model.modules():
         if hasattr(mod, "fused_node") and hasattr(mod, "temb_cemb_proj"):  # DDPM ResnetBlock: one autograd node
-            mod.fused_node = _BLOCK_NODES[0]
+            mod.fused_node = True
     own_gemm = [m for m in model.modules() if hasattr(m, "own_gemm")]
     if own_gemm and _OWN_GEMM[0]:
         # diffusion U-Nets: attention and every Linear layer on this package's fp32 MFMA GEMM (K15, gemm.py) as well
         from .gemm import use_salun_linears
-        parts = os.environ.get("SALUN_OWN_GEMM_PARTS", "linear,grouped,attn").split(",")  # A/B / debugging
         for m in own_gemm:
-            is_attn = hasattr(m, "proj_out") or hasattr(m, "to_q")
-            m.own_gemm = ("attn" in parts) if is_attn else ("grouped" in parts)
-        if "linear" in parts:
-            use_salun_linears(model)
+            m.own_gemm = True
+        use_salun_linears(model)
     owners = {id(m.conv) for m in model.modules() if getattr(m, "use_mfma", False) and hasattr(m, "conv")}
     for mod in model.modules():
         if type(mod) is nn.Conv2d and _eligible(mod) and id(mod) not in owners:
@@ -170,8 +161,7 @@ def use_salun_convs(model: nn.Module) -> int:
             n += 1
     # 3x3 / stride 1 / pad 1 layers: forward and backward-data on the LDS-DMA ring kernel (csrc/salun_conv_ring.hip),
     # which reads packed weight images — all layers of the model re-packed in one launch per optimizer step
-    if _RING[0]:
-        ringpack.register([m.weight for m in model.modules()
-                           if isinstance(m, nn.Conv2d) and _eligible(m) and m.kernel_size == (3, 3)
-                           and m.stride == (1, 1) and m.padding == (1, 1)])
+    ringpack.register([m.weight for m in model.modules()
+                       if isinstance(m, nn.Conv2d) and _eligible(m) and m.kernel_size == (3, 3)
+                       and m.stride == (1, 1) and m.padding == (1, 1)])
     return n

@@ -174,10 +174,9 @@ def _tokens_nhwc(t: torch.Tensor, C: int) -> torch.Tensor:
     return t.view(1, M // 8, 8, C) if M % 8 == 0 else t.view(1, M, 1, C)
 
 
-# SALUN_LINEAR_GEMM=0: keep the Linear layers on the K11 1x1 convolution kernels (A/B switch); variant pins a K16 tile
+# SALUN_LINEAR_GEMM=0: keep the Linear layers on the K11 1x1 convolution kernels (A/B switch)
 import os as _os
 _USE_K16 = [_os.environ.get("SALUN_LINEAR_GEMM", "1") != "0"]
-_K16_VARIANT = [int(_os.environ.get("SALUN_LINEAR_GEMM_VARIANT", "0"))]
 
 
 def _al16(t) -> bool:
@@ -199,7 +198,7 @@ class _LinearBF16Fn(FastFunction):
         # parameter ahead of them), in which case the K11 kernels, which take any alignment, serve the layer
         k16 = (_USE_K16[0] and ops.gemm_bf16_supported(M, K, C) and _al16(x2) and _al16(bias) and _al16(a2))
         if k16:
-            y = ops.gemm_bf16_nt(x2, mod.packed_weight().view(K, C), bias, a2, _K16_VARIANT[0])
+            y = ops.gemm_bf16_nt(x2, mod.packed_weight().view(K, C), bias, a2)
         else:
             xn = x2.view(1, M // 8, 8, C) if M % 8 == 0 else x2.view(1, M, 1, C)
             an = a2.view(1, xn.shape[1], xn.shape[2], K) if a2 is not None else None
@@ -236,7 +235,7 @@ class _LinearBF16Fn(FastFunction):
                     dw = got.view(K, C)
         if ctx.needs_input_grad[0]:
             if _USE_K16[0] and ops.gemm_bf16_supported(M, C, K) and _al16(dy2):
-                dx = ops.gemm_bf16_nt(dy2, mod.packed_weight_t(), None, None, _K16_VARIANT[0]).view(ctx.x_shape)
+                dx = ops.gemm_bf16_nt(dy2, mod.packed_weight_t()).view(ctx.x_shape)
             else:
                 dx = ops.conv2d_bf16_backward_data(as_img(dy2, K), mod.packed_weight(), (1,) + tuple(as_img(x2, C).shape[1:]),
                                                    1, 1, 0).view(ctx.x_shape)

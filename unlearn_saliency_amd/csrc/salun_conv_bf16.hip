@@ -484,9 +484,6 @@ struct WgArgs {
 // the SD layer table against one workgroup per CU with a ring of three register sets (same box, alternated,
 // profiles/r05_convbench_bf16_ab.txt).  The stride-2 kernel stages a 17x17 patch (90 KB double buffered): two
 // workgroups do not fit a CU's LDS, the single set then loses 7 - 10 %, so it (and the 1x1 fallback) keeps the ring.
-#ifndef SALUN_BF16_WGRAD_EXP
-#define SALUN_BF16_WGRAD_EXP 0  // timing experiments only (profiles/r05_wgrad_phases.txt): 1 = no stores, 2 = no reduction
-#endif
 template <int R, int ST>
 __global__ __launch_bounds__(256, (R == 3 && ST == 1) ? 2 : 1) void conv_bf16_wgrad(const WgArgs g) {
   constexpr bool PAIRED = R == 3 && ST == 1;   // two workgroups per CU, one register set
@@ -504,11 +501,7 @@ __global__ __launch_bounds__(256, (R == 3 && ST == 1) ? 2 : 1) void conv_bf16_wg
   const int wk = wave & 1, wc = wave >> 1;
   const int k0 = blockIdx.x * 64, c0 = blockIdx.y * 64, split = blockIdx.z;
   const int cb = split * g.per_split;
-#if SALUN_BF16_WGRAD_EXP == 2
-  const int ce = cb;  // timing experiment: no reduction at all, the epilogue alone
-#else
   const int ce = min(g.chunks, cb + g.per_split);
-#endif
 
   // Staging (round 5).  36 bf16 MFMAs per chunk are ~1,150 cycles — less than a trip to HBM — so ONE wave per SIMD with a
   // single chunk of prefetch left the matrix pipe waiting on loads.  The ring variant keeps three register sets over the
@@ -689,22 +682,12 @@ __global__ __launch_bounds__(256, (R == 3 && ST == 1) ? 2 : 1) void conv_bf16_wg
 #pragma unroll
           for (int q = 0; q < 4; ++q)
 #pragma unroll
-            for (int t = 0; t < RS; ++t) {
-#if SALUN_BF16_WGRAD_EXP == 1
-              if (acc[t][4 * j + q] != 12345.678f) continue;
-#endif
-              dst[q * row + t] = old[q][t] + acc[t][4 * j + q];
-            }
+            for (int t = 0; t < RS; ++t) dst[q * row + t] = old[q][t] + acc[t][4 * j + q];
         } else {
 #pragma unroll
           for (int q = 0; q < 4; ++q)
 #pragma unroll
-            for (int t = 0; t < RS; ++t) {
-#if SALUN_BF16_WGRAD_EXP == 1
-              if (acc[t][4 * j + q] != 12345.678f) continue;
-#endif
-              dst[q * row + t] = acc[t][4 * j + q];
-            }
+            for (int t = 0; t < RS; ++t) dst[q * row + t] = acc[t][4 * j + q];
         }
       }
     }
@@ -717,9 +700,6 @@ __global__ __launch_bounds__(256, (R == 3 && ST == 1) ? 2 : 1) void conv_bf16_wg
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
         const int k = k0 + wk * 32 + (v & 3) + 8 * (v >> 2) + 4 * (lane >> 5);
-#if SALUN_BF16_WGRAD_EXP == 1
-        if (acc[t][v] != 12345.678f) continue;
-#endif
         if (k < g.K) dst[(size_t)k * g.C + c] = acc[t][v];
       }
     }

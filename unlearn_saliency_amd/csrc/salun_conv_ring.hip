@@ -31,12 +31,6 @@ namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __attribute__((address_space(3))) char *ring_lds_ptr_t;
 
-// Tuning switch (0 in the product build; tools/lab_build.sh builds A/B libraries with it — results are WRONG with a bit
-// set): conv3x3_wgrad_ring  1 no DMA after the first chunk   2 no MFMAs   4 no partial-sum stores
-#ifndef SALUN_WGR_EXP
-#define SALUN_WGR_EXP 0
-#endif
-
 constexpr int RCC = 8;      // reduction channels per chunk
 constexpr int RSTEPS = 36;  // k-steps per chunk: (RCC / 2) channel pairs x 9 taps
 constexpr int RGROUPS = 9;  // 16-byte A groups per chunk and 32-row tile (4 k-steps each)
@@ -539,13 +533,12 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_ring(const WgradRingArgs g)
 #pragma unroll
           for (int t = 0; t < 9; ++t) {
             const float bv = pick(t / 3 == 0 ? cur.b0 : t / 3 == 1 ? cur.b1 : cur.b2, e + t % 3);
-            if (!(SALUN_WGR_EXP & 2)) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[t], 0, 0, 0);
-            else asm volatile("" ::"v"(av), "v"(bv));
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[t], 0, 0, 0);
             if (t == 0) {
               // one DMA unit of the next chunk per MFMA step (first half of the chunk), between two MFMAs
               __builtin_amdgcn_sched_barrier(0);
               const int u = 4 * m + e;
-              if (u < NDW + NXW && more && !(SALUN_WGR_EXP & 1)) issue_unit(u, nxt_chunk, stage ^ 1);
+              if (u < NDW + NXW && more) issue_unit(u, nxt_chunk, stage ^ 1);
               __builtin_amdgcn_sched_barrier(0);
             }
           }
@@ -562,7 +555,6 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_ring(const WgradRingArgs g)
   static_assert(NDW + NXW <= 32, "one DMA unit per MFMA step");
   float *out = g.part + (size_t)split * K * C * 9;
   const int c = c0 + ct * 32 + lo;
-  if ((SALUN_WGR_EXP & 4) && K > 0) return;
 #pragma unroll
   for (int t = 0; t < 9; ++t)
 #pragma unroll

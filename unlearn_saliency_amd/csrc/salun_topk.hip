@@ -45,19 +45,9 @@
 #include <cmath>
 #include <cstdlib>
 
-// Timing switches (0 in the product build; profiles/r05_topk_experiments.txt was measured with run-time versions of
-// them — results are WRONG with any bit set, they only show where a kernel's time goes):
-//   k_main    8 no compaction   16 no mask stores   32 no software prefetch of the next chunk
-//   k_resolve 1 stop after the row sums   2 ... after the selection   4 no flush of the second-level histogram
-//   k_finish 64 stop after the prologue loads   128 ... after the two scans
-#ifndef SALUN_TOPK_EXP
-#define SALUN_TOPK_EXP 0
-#endif
-
 namespace {
 
 constexpr int MAXK = SALUN_MAX_THRESHOLDS;
-constexpr int TOPK_EXP = SALUN_TOPK_EXP;
 constexpr int D0_BINS = 2048;  // key >> 20
 constexpr int CHUNK_VEC = 4 * SALUN_BLOCK;  // float4 per chunk (4 sub-vectors per lane)
 constexpr int CHUNK = CHUNK_VEC * 4;        // 4096 elements: streaming / tie-ordering granule
@@ -530,17 +520,8 @@ __global__ __launch_bounds__(SALUN_BLOCK) void k_main(const float *__restrict__ 
     for (int u = 0; u < 4; ++u) {
       k[u][0] = key_of(x[u].x); k[u][1] = key_of(x[u].y); k[u][2] = key_of(x[u].z); k[u][3] = key_of(x[u].w);
     }
-    if (TOPK_EXP & 32) {  // (timing experiment: no software prefetch — load this chunk now)
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        x[u] = __builtin_nontemporal_load(reinterpret_cast<const vf4 *>(acc) + c * CHUNK_VEC + u * SALUN_BLOCK + tid);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        k[u][0] = key_of(x[u].x); k[u][1] = key_of(x[u].y); k[u][2] = key_of(x[u].z); k[u][3] = key_of(x[u].w);
-      }
-    }
     const int64_t cn = c + gridDim.x;
-    if (cn < nfull && !(TOPK_EXP & 32)) {  // the next chunk's loads fly while this one is classified
+    if (cn < nfull) {  // the next chunk's loads fly while this one is classified
 #pragma unroll
       for (int u = 0; u < 4; ++u)
         x[u] = __builtin_nontemporal_load(reinterpret_cast<const vf4 *>(acc) + cn * CHUNK_VEC + u * SALUN_BLOCK + tid);
@@ -577,32 +558,30 @@ __global__ __launch_bounds__(SALUN_BLOCK) void k_main(const float *__restrict__ 
             jsel[u][e] = ((k[u][e] - lo[j]) <= w) ? (uint32_t)j : jsel[u][e];
             gtc[j] += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(k[u][e] > hi[j]));
           }
-          if (!VO && !(TOPK_EXP & 16))
+          if (!VO)
             __builtin_nontemporal_store(bits, reinterpret_cast<uint32_t *>(mp.m[j]) + c * CHUNK_VEC + u * SALUN_BLOCK + tid);
         }
       }
-      if (!(TOPK_EXP & 8)) {
 #pragma unroll
-        for (int u = 0; u < 4; ++u)
+      for (int u = 0; u < 4; ++u)
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const uint32_t js = jsel[u][e];
-            if (js != JSEL_NONE) {
-              const uint32_t key = k[u][e];
-              const uint32_t pos = atomicAdd(&s_cnt[js], 1u);
-              atomicAdd(&(&s_hist[0][0])[js * BINS_A + ((key - s_lo[js]) >> s_sh[js])], 1u);
-              if (store) {
-                const uint2 ent = make_uint2(key, idx0 + (uint32_t)(u * 1024 + e));
-                if (pos < cap) {
-                  *reinterpret_cast<uint2 *>(reinterpret_cast<char *>(slab0) + (size_t)((js * cap + pos) << 3)) = ent;
-                } else {
-                  const uint32_t sp_pos = atomicAdd(&fs->spill_cnt[js], 1u);
-                  if (sp_pos < spill_cap) spill[(size_t)js * spill_cap + sp_pos] = ent;
-                }
+        for (int e = 0; e < 4; ++e) {
+          const uint32_t js = jsel[u][e];
+          if (js != JSEL_NONE) {
+            const uint32_t key = k[u][e];
+            const uint32_t pos = atomicAdd(&s_cnt[js], 1u);
+            atomicAdd(&(&s_hist[0][0])[js * BINS_A + ((key - s_lo[js]) >> s_sh[js])], 1u);
+            if (store) {
+              const uint2 ent = make_uint2(key, idx0 + (uint32_t)(u * 1024 + e));
+              if (pos < cap) {
+                *reinterpret_cast<uint2 *>(reinterpret_cast<char *>(slab0) + (size_t)((js * cap + pos) << 3)) = ent;
+              } else {
+                const uint32_t sp_pos = atomicAdd(&fs->spill_cnt[js], 1u);
+                if (sp_pos < spill_cap) spill[(size_t)js * spill_cap + sp_pos] = ent;
               }
             }
           }
-      }
+        }
       continue;
     }
 #pragma unroll
@@ -621,10 +600,10 @@ __global__ __launch_bounds__(SALUN_BLOCK) void k_main(const float *__restrict__ 
           total += (uint32_t)__builtin_popcountll(bal[u * 4 + e]);
           gtc[j] += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(k[u][e] > hi[j]));
         }
-        if (!VO && !(TOPK_EXP & 16))
+        if (!VO)
           __builtin_nontemporal_store(bits, reinterpret_cast<uint32_t *>(mp.m[j]) + c * CHUNK_VEC + u * SALUN_BLOCK + tid);
       }
-      if (total && !(TOPK_EXP & 8)) {  // wave-uniform
+      if (total) {  // wave-uniform
         uint32_t base = 0;
         if (lane == 0) base = atomicAdd(&s_cnt[j], total);
         base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
@@ -833,7 +812,6 @@ __global__ __launch_bounds__(1024) void k_resolve(FastState *fs, const uint2 *__
   }
   if (failed) return;  // already decided (a u16 row counter wrapped in k_main): the full scan redoes the job
   if (mode != MODE_GE) return;  // nothing / everything selected: no candidates, k_finish publishes
-  if (TOPK_EXP & 1) return;  // (timing experiment: loads + row sums only)
   if (tid == 0) { s_n = 0; s_ok = 0; }
   for (int i = tid; i < HIST2_BINS; i += 1024) s_h2[i] = 0;
   __syncthreads();
@@ -882,7 +860,6 @@ __global__ __launch_bounds__(1024) void k_resolve(FastState *fs, const uint2 *__
   }
   __syncthreads();
   uint2 *seg = list2 + ((size_t)j * nseg + g) * seg_cap;
-  if (TOPK_EXP & 2) return;  // (timing experiment: ... + selection)
   if (s_ok) {
     const uint32_t lo2 = s_lo2, hi2 = s_hi2, sh2 = s_sh2;
     uint8_t *mask = mp.m[j];
@@ -936,7 +913,7 @@ __global__ __launch_bounds__(1024) void k_resolve(FastState *fs, const uint2 *__
   }
   __syncthreads();
   const uint32_t m = s_n;
-  if (m && !(TOPK_EXP & 4))
+  if (m)
     for (int i = tid; i < HIST2_BINS; i += 1024)
       if (s_h2[i]) atomicAdd(&fs->hist2[j][i], s_h2[i]);
   if (tid == 0) {
@@ -1011,7 +988,6 @@ __global__ __launch_bounds__(1024) void k_finish(FastState *fs, TopkPub *pub, co
     if (tid == 0 && f == 0) { pub->mode[j] = MODE_GE; pub->tau[j] = ZERO_KEY; pub->route = 1; }
     return;
   }
-  if (TOPK_EXP & 64) return;  // (timing experiment: prologue loads only)
   if (tid == 0) { s_found = 0; s_tau = 0; s_last = 0; s_n = 0; s_base = 0; }
   uint32_t n2;
   {  // offsets of the per-workgroup segments of the short list
@@ -1043,7 +1019,6 @@ __global__ __launch_bounds__(1024) void k_finish(FastState *fs, TopkPub *pub, co
     }
   }
   __syncthreads();
-  if (TOPK_EXP & 128) return;  // (timing experiment: ... + the two scans)
   uint32_t lo3 = lo2 + (s_b2 << sh2);
   uint32_t hi3 = lo3 + ((1u << sh2) - 1u);
   if (hi3 > hi2 || hi3 < lo3) hi3 = hi2;

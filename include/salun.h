@@ -199,6 +199,27 @@ int salun_masked_adam_step_coef(float *p /*dev*/, const float *g /*dev*/, float 
                                 double max_norm, double gscale, const float *coef /*dev [2]*/, double b1, double b2,
                                 double eps, double wd, int64_t n, salun_stream_t stream);
 
+/* ----------------------------------------------------------------- K20 --
+ * Masked Adam step + EMA of the parameters in ONE pass (training from scratch: DDPM/runners/diffusion.py:238-250,
+ * 445-457 with DDPM/models/ema.py:28-36).  Per element: exactly salun_masked_adam_step (same device function, p / m1 / v
+ * bit-identical to it), then with the new p still in registers
+ *     shadow = shadow + w * (p - shadow),   w = (float)(1 - mu)      (1 - mu evaluated in double on the host)
+ * which is Tensor.lerp_(p, 1 - mu) for a weight below 0.5 (ATen/native/Lerp.h): the product and the sum are one fused
+ * multiply-add, as in ATen's device code for gfx950 (v_sub_f32, then v_fma_f32).
+ * p, g, m1, v, shadow must be five distinct buffers (SALUN_EINVAL otherwise, nothing is launched).
+ * The two entry points mirror salun_masked_adam_step / salun_masked_adam_step_coef.
+ * Algorithmic traffic: 36 B / element (read p, g, m1, v, shadow; write p, m1, v, shadow); 37 with a mask —
+ * against 28 (29) + 12 for the Adam kernel followed by lerp_. */
+int salun_adam_ema_step(float *p /*dev*/, const float *g /*dev*/, float *m1 /*dev*/, float *v /*dev*/,
+                        float *shadow /*dev*/, const uint8_t *mask /*dev or NULL*/,
+                        const float *sqnorm /*dev or NULL*/, double max_norm, double gscale, double lr, double b1,
+                        double b2, double eps, double wd, double mu, int step, int64_t n, salun_stream_t stream);
+int salun_adam_ema_step_coef(float *p /*dev*/, const float *g /*dev*/, float *m1 /*dev*/, float *v /*dev*/,
+                             float *shadow /*dev*/, const uint8_t *mask /*dev or NULL*/,
+                             const float *sqnorm /*dev or NULL*/, double max_norm, double gscale,
+                             const float *coef /*dev [2]*/, double b1, double b2, double eps, double wd, double mu,
+                             int64_t n, salun_stream_t stream);
+
 /* ------------------------------------------------------------------ K6 --
  * Forward diffusion sample:  xt = x0*sqrt_ab[t[b]] + e*sqrt_1mab[t[b]]
  * Replaces  DDPM/functions/losses.py:31-32, runners/diffusion.py:558-559,973-974.

@@ -1,6 +1,6 @@
-"""CIFAR-10 class-split loaders for the DDPM forget / remain sets (reference DDPM/datasets/__init__.py:120-177,
-241-255).  The reference materialises both splits once as Python lists of (ToTensor image, label) with the
-random flip frozen at materialisation time; here both splits are device-resident fp32 tensors built once
+"""CIFAR-10 loaders for the DDPM runs: the whole training set (`get_dataset`, reference DDPM/datasets/__init__.py:30-77)
+and the class-split forget / remain sets (reference :120-177, 241-255).  The reference materialises both splits once
+as Python lists of (ToTensor image, label) with the random flip frozen at materialisation time; here both splits are device-resident fp32 tensors built once
 (flip drawn once, like the reference) and batches are index gathers on the GPU.  Falls back to the
 counter-based synthetic CIFAR-shaped set when the dataset files are absent (no network on the GPU box)."""
 from __future__ import annotations
@@ -15,9 +15,10 @@ from ... import dist as sdist
 class TensorLoader:
     """Shuffling batch iterator over device tensors (x: (N,3,32,32) fp32 in [0,1], c: (N,) int64)."""
 
-    def __init__(self, x, c, batch_size, shuffle=True, rank=0, world_size=1):
+    def __init__(self, x, c, batch_size, shuffle=True, rank=0, world_size=1, flip=False):
         self.x, self.c, self.batch_size, self.shuffle = x, c, int(batch_size), shuffle
         self.rank, self.world_size = rank, world_size
+        self.flip = flip  # RandomHorizontalFlip(0.5) per sample and pass, drawn for the global batch like the order
         self.last_shard = None  # (lo, hi, b): this rank holds samples [lo, hi) of the global batch of b just yielded
 
     def __len__(self):
@@ -34,22 +35,42 @@ class TensorLoader:
             lo, hi = sdist.balanced_slice(b, self.rank, self.world_size) if self.world_size > 1 else (0, b)
             self.last_shard = (lo, hi, b)
             idx = idx[lo:hi]
-            yield self.x[idx], self.c[idx]
+            x = self.x[idx]
+            if self.flip:
+                mirror = (torch.rand(b, generator=g) < 0.5)[lo:hi].to(x.device)
+                x = torch.where(mirror[:, None, None, None], x.flip(3), x)
+            yield x, self.c[idx]
+
+
+def _train_arrays(config, synthetic):
+    """(x uint8 NHWC, y int64) of the CIFAR-10 training set, or of its synthetic stand-in."""
+    use_syn = synthetic if synthetic is not None else not have_cifar10(config.data.path)
+    (x, y), _ = synthetic_cifar10() if use_syn else _load_cifar10_files(config.data.path)
+    return x, y
+
+
+def _to_device(x, y, device):
+    xt = torch.from_numpy(np.ascontiguousarray(x)).to(device).permute(0, 3, 1, 2).float().div_(255).contiguous()
+    return xt, torch.from_numpy(y).to(device)
+
+
+def get_dataset(args, config, device=None, synthetic=None):
+    """-> loader over the whole training set (`--mode train`): shuffled every pass; with `data.random_flip` each sample
+    is mirrored with probability 0.5 every time it is drawn, as the reference's transform does."""
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    xt, yt = _to_device(*_train_arrays(config, synthetic), device)
+    return TensorLoader(xt, yt, config.training.batch_size, True, sdist.rank(), sdist.world_size(),
+                        flip=bool(getattr(config.data, "random_flip", True)))
 
 
 def get_forget_dataset(args, config, label_to_drop, device=None, synthetic=None):
     """-> (remain_loader, forget_loader) split by class `label_to_drop`."""
     device = device or torch.device("cuda", torch.cuda.current_device())
-    use_syn = synthetic if synthetic is not None else not have_cifar10(config.data.path)
-    if use_syn:
-        (x, y), _ = synthetic_cifar10()
-    else:
-        (x, y), _ = _load_cifar10_files(config.data.path)
+    x, y = _train_arrays(config, synthetic)
     if getattr(config.data, "random_flip", True):  # frozen once, as in the reference's materialised lists
         flip = np.random.rand(len(x)) < 0.5
         x = np.where(flip[:, None, None, None], x[:, :, ::-1, :], x)
-    xt = torch.from_numpy(np.ascontiguousarray(x)).to(device).permute(0, 3, 1, 2).float().div_(255).contiguous()
-    yt = torch.from_numpy(y).to(device)
+    xt, yt = _to_device(x, y, device)
     forget = yt == int(label_to_drop)
     print(int((~forget).sum()), int(forget.sum()))
     rk, ws = sdist.rank(), sdist.world_size()

@@ -4,8 +4,9 @@ name -> tensor dict, DataParallel wrappers unwrapped).
 
 The shadow is ONE flat fp32 vector in `named_parameters()` order (the arena's layout): `update` is a single
 `lerp_` over it when the module's parameters live in a flat arena (one launch for 38.6 M weights instead of 334 x 3),
-and a per-tensor loop over views of it otherwise.  `state_dict()` hands out per-name views, so checkpoints keep the
-reference's format.
+and a per-tensor loop over views of it otherwise.  `attach_to(optimizer, module)` goes one step further: the optimizer's
+Adam launch advances the shadow itself (salun_adam_ema_step) and `update` becomes a no-op for that step.
+`state_dict()` hands out per-name views, so checkpoints keep the reference's format.
 """
 from __future__ import annotations
 
@@ -25,6 +26,7 @@ class EMAHelper(object):
         self.shadow = {}
         self._flat = None
         self._names = []
+        self._folded = False  # one-shot: the optimizer's last step already advanced the shadow (note_folded)
 
     def _trainable(self, module):
         return [(n, p) for n, p in _unwrap(module).named_parameters() if p.requires_grad]
@@ -51,7 +53,25 @@ class EMAHelper(object):
             return a.params
         return None
 
+    def attach_to(self, optimizer, module) -> bool:
+        """Let `optimizer` (FusedMaskedAdam) advance the shadow inside its own launch.  Only when the shadow lines up
+        with the optimizer's arena (`_arena_params`); otherwise nothing is attached and `update` keeps its own pass."""
+        flat = self._arena_params(module)
+        if flat is None or not hasattr(optimizer, "attach_ema") or getattr(optimizer, "arena", None) is None \
+                or optimizer.arena.params.data_ptr() != flat.data_ptr() or not 0.5 < self.mu <= 1.0:
+            return False
+        optimizer.attach_ema(self._flat, self.mu, helper=self)
+        return True
+
+    def note_folded(self):
+        """Called by the optimizer after a step that advanced the shadow: the next `update` is that step's and is
+        consumed without touching the shadow; any further `update` applies the average as usual."""
+        self._folded = True
+
     def update(self, module):
+        if self._folded:
+            self._folded = False
+            return
         flat = self._arena_params(module)
         if flat is not None:
             self._flat.lerp_(flat, 1.0 - self.mu)  # shadow = mu * shadow + (1 - mu) * param, one pass
@@ -60,8 +80,11 @@ class EMAHelper(object):
             self.shadow[name].mul_(self.mu).add_(param.data, alpha=1.0 - self.mu)
 
     def ema(self, module):
-        for name, param in self._trainable(module):
-            param.data.copy_(self.shadow[name])
+        from ... import weightimg
+        with torch.no_grad():
+            for name, param in self._trainable(module):
+                param.copy_(self.shadow[name])
+        weightimg.params_written()  # the packed weight images of `module` are stale from here on
 
     def ema_copy(self, module):
         inner = _unwrap(module)

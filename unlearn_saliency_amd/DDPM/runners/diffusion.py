@@ -1,5 +1,6 @@
-"""`Diffusion` runner: the three hot entry points of the reference's DDPM/runners/diffusion.py —
+"""`Diffusion` runner: the entry points of the reference's DDPM/runners/diffusion.py —
 
+    train() / retrain() the original model / the remaining classes only (reference :194-270, :399-480)
     generate_mask()     Phase A for the CFG-DDPM U-Net           (reference :933-1039)
     saliency_unlearn()  masked ε-MSE unlearning loop (rl / ga)   (reference :482-619)
     save_fim()          diagonal empirical Fisher                 (reference :101-191)
@@ -7,8 +8,8 @@
 — same constructor (`Diffusion(args, config)`), same `args` / YAML fields, same artefacts
 (`results/cifar10/mask/{label}/with_0.5.pt` with `module.`-prefixed int64 tensors; `ckpts/ckpt.pth` =
 `[model_state, optimizer_state, step]`; `fisher_dict.pkl`).  `sample()` and its modes (reference :621-931) write
-the folders of PNGs the evaluation and `save_fim` / `train_forget` read.  Pre-training / FID stay
-out of scope.
+the folders of PNGs the evaluation and `save_fim` / `train_forget` read.  FID stays out of scope
+(SURVEY.md §2 D7).
 
 What is different underneath (MI355X-first):
   * one process per GPU + RCCL instead of nn.DataParallel's per-step parameter broadcast / output gather;
@@ -35,7 +36,7 @@ from ... import dist as sdist
 from ... import draws, hostperf, ops
 from ...flat import FlatArena, arena_of
 from ...streams import concurrent_stream
-from ..datasets import data_transform, get_forget_dataset
+from ..datasets import data_transform, get_dataset, get_forget_dataset
 from ..functions import cycle, get_optimizer
 from ..functions.losses import loss_registry_conditional, q_sample
 from ..models.diffusion import Conditional_Model
@@ -130,8 +131,13 @@ class Diffusion(object):
         self.args, self.config = args, config
         if not torch.cuda.is_available():
             raise RuntimeError("the DDPM hot path needs a ROCm device (no CPU fallback)")
+        self._setup(torch.device("cuda", torch.cuda.current_device()))
+
+    def _setup(self, device):
+        """The schedule tables on `device` (the constructor passes the current GPU)."""
+        config = self.config
         draws.seed(None)  # a run's dropout keys restart from (torch seed, step 0): main.py seeds torch before this
-        self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = device
         self.model_var_type = config.model.var_type
         betas = get_beta_schedule(beta_schedule=config.diffusion.beta_schedule,
                                   beta_start=config.diffusion.beta_start, beta_end=config.diffusion.beta_end,
@@ -341,6 +347,101 @@ class Diffusion(object):
         helper = EMAHelper(mu=self.config.model.ema_rate)
         helper.register(model)
         return helper
+
+    # ------------------------------------------------------- training from scratch: train / retrain
+    def train_step(self, model, optimizer, batch, loader=None):
+        """One iteration of the reference's train / retrain loop body (:216-247, :423-454): ε-MSE with label drop on one
+        batch, clip -> Adam (-> EMA when the optimizer carries the shadow).  Returns the loss tensor (no host sync)."""
+        config = self.config
+        x, c = batch
+        draws.next_step()
+        sd = ShardDraws(loader, x.size(0))  # global-batch draws, sliced (data parallel)
+        x = data_transform(config, x.to(self.device))
+        e = sd.randn_like(x)
+        t = sd.timesteps(self.num_timesteps, self.device)
+        with sd:
+            loss = loss_registry_conditional[config.model.type](model, x, t, c, e, self.betas)
+        if sd.weight != 1.0:
+            loss = loss * sd.weight
+        optimizer.zero_grad()
+        loss.backward()
+        clip = getattr(config.optim, "grad_clip", None)
+        if clip:
+            optimizer.clip_grad_norm_(clip)
+        optimizer.step()
+        return loss
+
+    def _snapshot_model(self, model, ema_helper):
+        """The model a snapshot is sampled from (reference :267-268): the EMA copy, or a copy of the weights as they are."""
+        if ema_helper is not None:
+            test_model = ema_helper.ema_copy(model)
+        else:
+            test_model = type(model)(model.config).to(self.device)
+            test_model.load_state_dict(model.state_dict())
+        if not getattr(self.args, "library_conv", False):
+            from ...conv import use_salun_convs
+            use_salun_convs(test_model)
+        return test_model.eval()
+
+    def _train(self, loader, model=None):
+        """The loop `train` and `retrain` share — they differ in the loader only (`model`: start from these weights
+        instead of a fresh initialisation).  Every `snapshot_freq` steps rank 0
+        writes `ckpt.pth` = [model, optimizer, step, ema] (model keys with the `module.` prefix) and the grid of samples
+        `sample-<step>.png` from the EMA copy."""
+        args, config = self.args, self.config
+        data_iter = cycle(loader)
+        if model is None:
+            model = Conditional_Model(config).to(self.device)  # a fresh initialisation, as in the reference
+        if not getattr(args, "library_conv", False):
+            from ...conv import use_salun_convs
+            use_salun_convs(model)  # fp32 MFMA convolution kernels instead of the library's heuristics
+        arena = arena_of(model)
+        optimizer = get_optimizer(config, arena=arena)
+        ema_helper = self._ema(model)
+        if ema_helper is not None:
+            ema_helper.attach_to(optimizer, model)  # the Adam launch advances the shadow; update() below is then a no-op
+        model.train()
+        start = time.time()
+        self.last_optimizer, self.last_ema = optimizer, ema_helper
+        self.step_losses = []  # device scalars of the last `keep_losses` steps (no host sync; diagnostics / parity tests)
+        keep_losses = int(getattr(args, "keep_losses", 64))
+        hostperf.freeze_gc()
+        for step in range(0, config.training.n_iters):
+            model.train()
+            loss = self.train_step(model, optimizer, next(data_iter), loader)
+            self.step_losses.append(loss.detach())
+            if len(self.step_losses) > keep_losses:
+                self.step_losses.pop(0)
+            if ema_helper is not None:
+                ema_helper.update(model)
+            if (step + 1) % config.training.log_freq == 0:
+                end = time.time()
+                logging.info(f"step: {step}, loss: {loss.item()}, time: {end - start}")
+                start = time.time()
+            if (step + 1) % config.training.snapshot_freq == 0:
+                if sdist.rank() == 0:
+                    states = [add_prefix(model.state_dict()), optimizer.state_dict(), step]
+                    if ema_helper is not None:
+                        states.append(ema_helper.state_dict())
+                    torch.save(states, os.path.join(config.ckpt_dir, "ckpt.pth"))
+                    test_model = self._snapshot_model(model, ema_helper)
+                    self.sample_visualization(test_model, step, args.cond_scale)
+                    del test_model
+                sdist.barrier()
+        return model
+
+    def train(self):
+        """`--mode train`: the original class-conditional model on the whole training set (reference :194-270)."""
+        args, config = self.args, self.config
+        self._train_loader = get_dataset(args, config, device=self.device,
+                                         synthetic=True if getattr(args, "synthetic", False) else None)
+        return self._train(self._train_loader)
+
+    def retrain(self):
+        """`--mode retrain`: the same recipe on every class but `args.label_to_forget` (reference :399-480) — the model
+        unlearning is compared against."""
+        remain_loader, _ = self._loaders()
+        return self._train(remain_loader)
 
     # ------------------------------------------------------------------ sampling (evaluation of an unlearned model)
     def sample_image(self, x, model, c, cond_scale, last=True, fused=False, image_ids=None):

@@ -1,9 +1,10 @@
 """`python train.py --config cifar10_saliency_unlearn.yml --ckpt_folder F --label_to_forget 0
 --mode generate_mask|saliency_unlearn [--mask_path M --alpha 1e-3 --method rl]`
+`python train.py --config cifar10_train.yml --mode train` / `--mode retrain --label_to_forget 0`
 
-Same flags as the reference's DDPM/train.py:15-93.  Modes on the SalUn hot path are implemented
-(generate_mask, saliency_unlearn); train / forget / retrain are pre-training and EWC baselines
- and exit with a scope note.
+Same flags and the same five modes as the reference's DDPM/train.py:15-93: train (the original model), retrain (every
+class but `--label_to_forget`: the model unlearning is compared against), forget (EWC baseline),
+generate_mask and saliency_unlearn (the SalUn hot path).
 Multi-GPU: launch with torchrun (one process per GPU); the reference's nn.DataParallel is not used."""
 import argparse
 import logging
@@ -92,9 +93,12 @@ def main(argv=None):
             runner.generate_mask()
         elif args.mode == "forget":  # EWC / Selective Amnesia on the fused penalty kernel
             runner.train_forget()
+        elif args.mode == "train":
+            runner.train()
+        elif args.mode == "retrain":
+            runner.retrain()
         else:
-            raise NotImplementedError(f"--mode {args.mode}: pre-training / retrain are outside the SalUn hot "
-                                      "path of this build (SURVEY.md §2 D1)")
+            raise ValueError(f"unknown --mode {args.mode!r} (train | forget | retrain | saliency_unlearn | generate_mask)")
     except Exception:
         logging.error(traceback.format_exc())
         return 1

@@ -1,6 +1,7 @@
 // salun_update.hip — HBM-bound element-wise kernels over the flat parameter arena:
 //   K1 saliency accumulate, K3+K4 masked SGD-momentum, K5 grad sq-norm + masked Adam,
-//   K7 Fisher square-accumulate.   gfx950 / CDNA4, compiled with -ffp-contract=off.
+//   K7 Fisher square-accumulate, K20 masked Adam + EMA shadow in one pass.
+//   gfx950 / CDNA4, compiled with -ffp-contract=off.
 //
 // Streaming shape shared by all of them: 256-thread workgroups (one wave per SIMD),
 // each workgroup walks "tiles" of UNROLL x 256 float4 (= 4096 floats for UNROLL 4)
@@ -341,6 +342,102 @@ int launch_adam(const AdamArgs &a, bool vec, hipStream_t st) {
   return SALUN_OK;
 }
 
+// ----------------------------------------------------------------------- K20 ----
+// K5's Adam step with the EMA shadow of the parameters updated in the same pass: the new p never leaves the registers
+// between the two (36 B / element in one launch instead of 28 + 12 in two).  adam_elem is K5's, untouched.
+struct AdamEmaArgs {
+  AdamArgs a;
+  float *shadow;
+  float w;  // 1 - mu, evaluated in double on the host
+};
+
+// Tensor.lerp_(p, w) for w < 0.5 (ATen/native/Lerp.h): shadow + w * (p - shadow).  ATen's device code is compiled with
+// floating-point contraction on, so its product and sum are ONE fused multiply-add; this file is compiled with
+// contraction off, so the fma is written out.
+__device__ __forceinline__ float ema_elem(float sh, float p, float w) { return __builtin_fmaf(w, p - sh, sh); }
+
+template <bool HAS_MASK, bool HAS_WD, bool VEC>
+__global__ __launch_bounds__(SALUN_BLOCK) void k_adam_ema(AdamEmaArgs e) {
+  AdamArgs &a = e.a;
+  const float s = a.sqnorm ? salun_clip_coef(*a.sqnorm, a.max_norm) : a.gscale;
+  if (a.coef) { a.bc2_sqrt = a.coef[0]; a.neg_step_size = a.coef[1]; }
+  const float w = e.w;
+  if (VEC) {
+    const int64_t nvec = a.n >> 2;
+    const int64_t ntile = (nvec + TILE_VEC - 1) / TILE_VEC;
+    for (int64_t t = blockIdx.x; t < ntile; t += gridDim.x) {
+      const int64_t base = t * TILE_VEC + threadIdx.x;
+      float4 pv[UNROLL], gv[UNROLL], mv1[UNROLL], vv[UNROLL], sv[UNROLL];
+      uint32_t mk[UNROLL];
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) {
+        const int64_t v = base + u * SALUN_BLOCK;
+        if (v < nvec) {
+          mk[u] = HAS_MASK ? ldm(a.mask, v) : 0x01010101u;
+          pv[u] = ld4(a.p, v);
+          gv[u] = ld4_nt(a.g, v);
+          mv1[u] = ld4(a.m1, v);
+          vv[u] = ld4(a.v, v);
+          sv[u] = ld4(e.shadow, v);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) {
+        const int64_t v = base + u * SALUN_BLOCK;
+        if (v < nvec) {
+          const uint32_t mm = mk[u];
+          adam_elem<HAS_WD>(pv[u].x, gv[u].x, mv1[u].x, vv[u].x, (mm & 0x000000FFu) ? 1.f : 0.f, s, a);
+          adam_elem<HAS_WD>(pv[u].y, gv[u].y, mv1[u].y, vv[u].y, (mm & 0x0000FF00u) ? 1.f : 0.f, s, a);
+          adam_elem<HAS_WD>(pv[u].z, gv[u].z, mv1[u].z, vv[u].z, (mm & 0x00FF0000u) ? 1.f : 0.f, s, a);
+          adam_elem<HAS_WD>(pv[u].w, gv[u].w, mv1[u].w, vv[u].w, (mm & 0xFF000000u) ? 1.f : 0.f, s, a);
+          sv[u].x = ema_elem(sv[u].x, pv[u].x, w);
+          sv[u].y = ema_elem(sv[u].y, pv[u].y, w);
+          sv[u].z = ema_elem(sv[u].z, pv[u].z, w);
+          sv[u].w = ema_elem(sv[u].w, pv[u].w, w);
+          st4(a.p, v, pv[u]);
+          st4(a.m1, v, mv1[u]);
+          st4(a.v, v, vv[u]);
+          st4(e.shadow, v, sv[u]);
+        }
+      }
+    }
+    if (blockIdx.x == 0) {
+      const int64_t i = (nvec << 2) + threadIdx.x;
+      if (i < a.n) {
+        float p = a.p[i], m1 = a.m1[i], v = a.v[i];
+        adam_elem<HAS_WD>(p, a.g[i], m1, v, HAS_MASK ? (a.mask[i] ? 1.f : 0.f) : 1.f, s, a);
+        a.p[i] = p;
+        a.m1[i] = m1;
+        a.v[i] = v;
+        e.shadow[i] = ema_elem(e.shadow[i], p, w);
+      }
+    }
+  } else {
+    for (int64_t i = (int64_t)blockIdx.x * SALUN_BLOCK + threadIdx.x; i < a.n;
+         i += (int64_t)gridDim.x * SALUN_BLOCK) {
+      float p = a.p[i], m1 = a.m1[i], v = a.v[i];
+      adam_elem<HAS_WD>(p, a.g[i], m1, v, HAS_MASK ? (a.mask[i] ? 1.f : 0.f) : 1.f, s, a);
+      a.p[i] = p;
+      a.m1[i] = m1;
+      a.v[i] = v;
+      e.shadow[i] = ema_elem(e.shadow[i], p, w);
+    }
+  }
+}
+
+template <bool HAS_MASK, bool HAS_WD>
+int launch_adam_ema(const AdamEmaArgs &e, bool vec, hipStream_t st) {
+  if (vec) {
+    const int grid = salun_grid_for(e.a.n, TILE_ELEMS);
+    hipLaunchKernelGGL((k_adam_ema<HAS_MASK, HAS_WD, true>), dim3(grid), dim3(SALUN_BLOCK), 0, st, e);
+  } else {
+    const int grid = salun_grid_for(e.a.n, SALUN_BLOCK * 4);
+    hipLaunchKernelGGL((k_adam_ema<HAS_MASK, HAS_WD, false>), dim3(grid), dim3(SALUN_BLOCK), 0, st, e);
+  }
+  SALUN_LAUNCH_CHECK();
+  return SALUN_OK;
+}
+
 // ------------------------------------------------------------------------ K7 ----
 template <bool VEC>
 __global__ __launch_bounds__(SALUN_BLOCK) void k_fim_square_accumulate(float *__restrict__ F, float *__restrict__ tmp,
@@ -485,11 +582,9 @@ SALUN_EXPORT int salun_masked_adam_step_coef(float *p, const float *g, float *m1
   return masked_adam_impl(p, g, m1, v, mask, sqnorm, max_norm, gscale, 0.0, b1, b2, eps, wd, 1, coef, n, stream);
 }
 
-static int masked_adam_impl(float *p, const float *g, float *m1, float *v, const uint8_t *mask, const float *sqnorm,
-                            double max_norm, double gscale, double lr, double b1, double b2, double eps, double wd,
-                            int step, const float *coef, int64_t n, salun_stream_t stream) {
-  if (n < 0 || step < 1 || (n > 0 && (!p || !g || !m1 || !v))) return SALUN_EINVAL;
-  if (n == 0) return SALUN_OK;
+static AdamArgs adam_args(float *p, const float *g, float *m1, float *v, const uint8_t *mask, const float *sqnorm,
+                          double max_norm, double gscale, double lr, double b1, double b2, double eps, double wd,
+                          int step, const float *coef, int64_t n) {
   // Python-scalar arithmetic of torch.optim.adam._single_tensor_adam, in double.
   const double bc1 = 1.0 - pow(b1, (double)step);
   const double bc2 = 1.0 - pow(b2, (double)step);
@@ -502,6 +597,15 @@ static int masked_adam_impl(float *p, const float *g, float *m1, float *v, const
   a.bc2_sqrt = (float)sqrt(bc2);
   a.neg_step_size = (float)(-(lr / bc1));
   a.n = n;
+  return a;
+}
+
+static int masked_adam_impl(float *p, const float *g, float *m1, float *v, const uint8_t *mask, const float *sqnorm,
+                            double max_norm, double gscale, double lr, double b1, double b2, double eps, double wd,
+                            int step, const float *coef, int64_t n, salun_stream_t stream) {
+  if (n < 0 || step < 1 || (n > 0 && (!p || !g || !m1 || !v))) return SALUN_EINVAL;
+  if (n == 0) return SALUN_OK;
+  const AdamArgs a = adam_args(p, g, m1, v, mask, sqnorm, max_norm, gscale, lr, b1, b2, eps, wd, step, coef, n);
   const bool has_mask = mask != nullptr, has_wd = wd != 0.0;
   const bool vec = salun_aligned16(p) && salun_aligned16(g) && salun_aligned16(m1) && salun_aligned16(v) &&
                    (!has_mask || salun_aligned4(mask));
@@ -510,6 +614,49 @@ static int masked_adam_impl(float *p, const float *g, float *m1, float *v, const
   if (has_mask && !has_wd) return launch_adam<true, false>(a, vec, st);
   if (!has_mask && has_wd) return launch_adam<false, true>(a, vec, st);
   return launch_adam<false, false>(a, vec, st);
+}
+
+// K20: the five vectors are read and written by the same lane in one pass, so two of them sharing memory would make
+// the result depend on the store order; refused before any launch.
+static int adam_ema_impl(float *p, const float *g, float *m1, float *v, float *shadow, const uint8_t *mask,
+                         const float *sqnorm, double max_norm, double gscale, double lr, double b1, double b2, double eps,
+                         double wd, double mu, int step, const float *coef, int64_t n, salun_stream_t stream) {
+  if (n < 0 || step < 1 || (n > 0 && (!p || !g || !m1 || !v || !shadow))) return SALUN_EINVAL;
+  if (n == 0) return SALUN_OK;
+  const void *bufs[5] = {p, m1, v, shadow, g};
+  for (int i = 0; i < 5; ++i)
+    for (int j = i + 1; j < 5; ++j)
+      if (bufs[i] == bufs[j]) return SALUN_EINVAL;
+  AdamEmaArgs e;
+  e.a = adam_args(p, g, m1, v, mask, sqnorm, max_norm, gscale, lr, b1, b2, eps, wd, step, coef, n);
+  e.shadow = shadow;
+  e.w = (float)(1.0 - mu);
+  const bool has_mask = mask != nullptr, has_wd = wd != 0.0;
+  const bool vec = salun_aligned16(p) && salun_aligned16(g) && salun_aligned16(m1) && salun_aligned16(v) &&
+                   salun_aligned16(shadow) && (!has_mask || salun_aligned4(mask));
+  hipStream_t st = salun_hip_stream(stream);
+  if (has_mask && has_wd) return launch_adam_ema<true, true>(e, vec, st);
+  if (has_mask && !has_wd) return launch_adam_ema<true, false>(e, vec, st);
+  if (!has_mask && has_wd) return launch_adam_ema<false, true>(e, vec, st);
+  return launch_adam_ema<false, false>(e, vec, st);
+}
+
+SALUN_EXPORT int salun_adam_ema_step(float *p, const float *g, float *m1, float *v, float *shadow, const uint8_t *mask,
+                                     const float *sqnorm, double max_norm, double gscale, double lr, double b1,
+                                     double b2, double eps, double wd, double mu, int step, int64_t n,
+                                     salun_stream_t stream) {
+  if (step < 1) return SALUN_EINVAL;
+  return adam_ema_impl(p, g, m1, v, shadow, mask, sqnorm, max_norm, gscale, lr, b1, b2, eps, wd, mu, step, nullptr, n,
+                       stream);
+}
+
+SALUN_EXPORT int salun_adam_ema_step_coef(float *p, const float *g, float *m1, float *v, float *shadow,
+                                          const uint8_t *mask, const float *sqnorm, double max_norm, double gscale,
+                                          const float *coef, double b1, double b2, double eps, double wd, double mu,
+                                          int64_t n, salun_stream_t stream) {
+  if (!coef) return SALUN_EINVAL;
+  return adam_ema_impl(p, g, m1, v, shadow, mask, sqnorm, max_norm, gscale, 0.0, b1, b2, eps, wd, mu, 1, coef, n,
+                       stream);
 }
 
 SALUN_EXPORT int salun_fim_square_accumulate(float *F, float *tmp, double n_data, int64_t n,

@@ -244,6 +244,42 @@ def masked_adam_step_coef(p, g, m1, v, mask, coef, beta1, beta2, eps, weight_dec
                                                  _stream()), "salun_masked_adam_step_coef")
 
 
+# ---------------------------------------------------------------------------- K20
+def adam_ema_step(p: torch.Tensor, g: torch.Tensor, m1: torch.Tensor, v: torch.Tensor, shadow: torch.Tensor,
+                  mask: Optional[torch.Tensor], lr: float, beta1: float, beta2: float, eps: float, weight_decay: float,
+                  mu: float, step: int, sqnorm: Optional[torch.Tensor] = None, max_norm: float = 1.0,
+                  gscale: float = 1.0) -> None:
+    """masked_adam_step, then shadow.lerp_(p, 1 - mu) on the new p, in one launch."""
+    n = p.numel()
+    assert g.numel() == n and m1.numel() == n and v.numel() == n and shadow.numel() == n
+    assert mask is None or mask.numel() == n
+    weightimg.params_written()
+    check(_lib.lib().salun_adam_ema_step(_dev(p, torch.float32, "p"), _dev(g, torch.float32, "g"),
+                                         _dev(m1, torch.float32, "exp_avg"), _dev(v, torch.float32, "exp_avg_sq"),
+                                         _dev(shadow, torch.float32, "shadow"), _dev(mask, torch.uint8, "mask", True),
+                                         _dev(sqnorm, torch.float32, "sqnorm", True), c_double(max_norm),
+                                         c_double(gscale), c_double(lr), c_double(beta1), c_double(beta2),
+                                         c_double(eps), c_double(weight_decay), c_double(mu), c_int(int(step)),
+                                         c_int64(n), _stream()), "salun_adam_ema_step")
+
+
+def adam_ema_step_coef(p, g, m1, v, shadow, mask, coef, beta1, beta2, eps, weight_decay, mu, sqnorm=None, max_norm=1.0,
+                       gscale=1.0) -> None:
+    """adam_ema_step with the step-dependent scalars read from device memory (adam_coefficients)."""
+    n = p.numel()
+    assert g.numel() == n and m1.numel() == n and v.numel() == n and shadow.numel() == n
+    assert mask is None or mask.numel() == n
+    weightimg.params_written()
+    check(_lib.lib().salun_adam_ema_step_coef(_dev(p, torch.float32, "p"), _dev(g, torch.float32, "g"),
+                                              _dev(m1, torch.float32, "exp_avg"), _dev(v, torch.float32, "exp_avg_sq"),
+                                              _dev(shadow, torch.float32, "shadow"),
+                                              _dev(mask, torch.uint8, "mask", True),
+                                              _dev(sqnorm, torch.float32, "sqnorm", True), c_double(max_norm),
+                                              c_double(gscale), _dev(coef, torch.float32, "coef"), c_double(beta1),
+                                              c_double(beta2), c_double(eps), c_double(weight_decay), c_double(mu),
+                                              c_int64(n), _stream()), "salun_adam_ema_step_coef")
+
+
 # ----------------------------------------------------------------------------- K6
 def qsample(x0: torch.Tensor, e: torch.Tensor, sqrt_ab: torch.Tensor, sqrt_1mab: torch.Tensor,
             t: torch.Tensor) -> torch.Tensor:

@@ -148,7 +148,8 @@ class FusedMaskedAdam(_FlatOptimizer):
     """clip_grad_norm_(max_norm) -> mask multiply -> torch.optim.Adam(amsgrad=False) step
     (DDPM/runners/diffusion.py:582-593, DDPM/functions/__init__.py:9-18) as two launches:
     `salun_grad_sqnorm` (deterministic reduction, result stays on the device) and
-    `salun_masked_adam_step` (reads the norm from device memory: no host sync anywhere)."""
+    `salun_masked_adam_step` (reads the norm from device memory: no host sync anywhere).
+    With `attach_ema` the second launch is `salun_adam_ema_step`, which also advances the EMA shadow."""
 
     _STATE_VECTORS = (("exp_avg", "exp_avg"), ("exp_avg_sq", "exp_avg_sq"))
     _STEP_KEY = True
@@ -164,6 +165,9 @@ class FusedMaskedAdam(_FlatOptimizer):
         self._sqnorm = torch.zeros(1, dtype=torch.float32, device=arena.device)
         self._step_dev = None  # device-resident step counter (use_device_step)
         self._coef = None
+        self._ema_shadow: Optional[torch.Tensor] = None  # attach_ema: the EMA update rides in the Adam launch
+        self._ema_mu = 0.0
+        self._ema_helper = None
 
     def use_device_step(self) -> None:
         """Keep Adam's step count (hence its bias corrections) on the device (salun_adam_coefficients advances it and
@@ -172,6 +176,23 @@ class FusedMaskedAdam(_FlatOptimizer):
         if self._step_dev is None:
             self._step_dev = torch.tensor([self.steps], dtype=torch.int64, device=self.arena.device)
             self._coef = torch.zeros(2, dtype=torch.float32, device=self.arena.device)
+
+    def attach_ema(self, shadow_flat: torch.Tensor, mu: float, helper=None) -> None:
+        """Fold `shadow_flat.lerp_(params, 1 - mu)` into every step() (salun_adam_ema_step: one pass over p, g, m1, v
+        and the shadow instead of the Adam kernel followed by lerp_).  `shadow_flat` is the flat fp32 EMA vector in
+        arena order (EMAHelper._flat).  `helper`, when given, is told after each folded step (`note_folded()`), so
+        that its next `update()` — the reference's call order is `optimizer.step(); ema_helper.update(model)` — does
+        not apply the average a second time."""
+        a = self.arena
+        if (shadow_flat.dtype != torch.float32 or shadow_flat.numel() != a.n or shadow_flat.device != a.params.device
+                or not shadow_flat.is_contiguous()):
+            raise ValueError("attach_ema: the shadow must be a contiguous fp32 vector of the arena's size on its device")
+        if not 0.5 < mu <= 1.0:
+            raise ValueError("attach_ema: mu must lie in (0.5, 1] (the lerp form of the average holds for 1 - mu < 0.5)")
+        self._ema_shadow, self._ema_mu, self._ema_helper = shadow_flat, float(mu), helper
+
+    def detach_ema(self) -> None:
+        self._ema_shadow, self._ema_helper = None, None
 
     def clip_grad_norm_(self, max_norm: float) -> torch.Tensor:
         """Arms clipping for the next step() and returns the squared norm (device tensor, no sync).
@@ -188,6 +209,9 @@ class FusedMaskedAdam(_FlatOptimizer):
         sq = None
         if self.grad_clip is not None:
             sq = ops.grad_sqnorm(self.arena.grads, self._sqnorm)
+        if self._ema_shadow is not None:
+            self._step_with_ema(g, sq)
+            return loss
         if self._step_dev is not None:
             ops.adam_coefficients(self._step_dev, g["lr"], g["betas"][0], g["betas"][1], self._coef)
             ops.masked_adam_step_coef(self.arena.params, self.arena.grads, self.exp_avg, self.exp_avg_sq, self.mask_u8,
@@ -198,3 +222,17 @@ class FusedMaskedAdam(_FlatOptimizer):
                              g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], self.steps,
                              sqnorm=sq, max_norm=self.grad_clip if self.grad_clip is not None else 1.0)
         return loss
+
+    def _step_with_ema(self, g: dict, sq: Optional[torch.Tensor]) -> None:
+        max_norm = self.grad_clip if self.grad_clip is not None else 1.0
+        if self._step_dev is not None:
+            ops.adam_coefficients(self._step_dev, g["lr"], g["betas"][0], g["betas"][1], self._coef)
+            ops.adam_ema_step_coef(self.arena.params, self.arena.grads, self.exp_avg, self.exp_avg_sq, self._ema_shadow,
+                                   self.mask_u8, self._coef, g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"],
+                                   self._ema_mu, sqnorm=sq, max_norm=max_norm)
+        else:
+            ops.adam_ema_step(self.arena.params, self.arena.grads, self.exp_avg, self.exp_avg_sq, self._ema_shadow,
+                              self.mask_u8, g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"],
+                              self._ema_mu, self.steps, sqnorm=sq, max_norm=max_norm)
+        if self._ema_helper is not None:
+            self._ema_helper.note_folded()

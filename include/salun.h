@@ -785,6 +785,35 @@ int salun_minmax(const float *x /*dev*/, int64_t n, float *lohi /*dev, 2*/, void
 int salun_images_to_u8(const float *x /*dev*/, uint8_t *out /*dev*/, int64_t B, int C, int HW, int rescaled,
                        const float *range /*dev, 2, or NULL*/, salun_stream_t stream);
 
+/* ----------------------------------------------------------------- K21 --
+ * The SD baselines (SD/train_scripts.py: train_esd; SD/ddim.py).
+ *
+ * salun_ldm_ddim_step: one reverse step of the LDM DDIM sampler on B latents of chw floats, fp32, one launch.
+ *   guided != 0: eps2 is the output of ONE batched U-Net pass over cat([x, x]): rows [0, B) unconditional (e_u), rows
+ *                [B, 2B) conditional (e_c), read in place;  e = e_u + scale * (e_c - e_u)
+ *   guided == 0: eps2 holds B rows, e = eps2, and scale must be 1 (else SALUN_EINVAL)
+ *   x0 = (x - c_s1m * e) / c_sqrt_at;  dir = c_dir * e;  x_prev = c_sqrt_aprev * x0 + dir [+ c_sigma * z]
+ * Each step is one correctly rounded fp32 operation in this order (no contraction, IEEE division).  The coefficients are
+ * fp32 values computed by the host from the DDIM tables (c_dir = sqrt(1 - a_prev - sigma^2)); the kernel recomputes
+ * none.  c_sigma == 0: the noise term is skipped and z may be NULL; c_sigma != 0 with z == NULL is SALUN_EINVAL.
+ * x0_out (optional) receives the x0 estimate; x_prev may be x.  Bound by launch latency at 4 x 64 x 64 latents. */
+int salun_ldm_ddim_step(const float *x /*dev*/, const float *eps2 /*dev, 2B or B rows*/, int guided, double scale,
+                        double c_s1m, double c_sqrt_at, double c_dir, double c_sqrt_aprev, double c_sigma,
+                        const float *z /*dev or NULL*/, float *x_prev /*dev*/, float *x0_out /*dev or NULL*/, int64_t B,
+                        int64_t chw, salun_stream_t stream);
+
+/* The ESD objective and its gradient: e_0p is ONE batched frozen pass, rows [0, B) = e_0 (unconditional), rows
+ * [B, 2B) = e_p (conditional); N = B * chw.
+ *   target = e_0 - ng * (e_p - e_0);  loss = sum((e_n - target)^2) / N;  d_e_n = (2 / N) * (e_n - target)
+ * target and d_e_n (both optional outputs) are sequences of correctly rounded fp32 operations; the sum folds fp32
+ * squares in fp64 in a fixed order (partials per 1024-element segment, folded by one workgroup; no float atomics).  Up to
+ * 64 segments — the workload's 4 x 64 x 64 latents are 16 — all of it is ONE launch of one workgroup; above, the
+ * segments spread over the chip and a second launch folds, in the same order. */
+size_t salun_esd_loss_workspace_bytes(int64_t B, int64_t chw);
+int salun_esd_loss(const float *e_n /*dev*/, const float *e_0p /*dev, 2B rows*/, int64_t B, int64_t chw,
+                   double negative_guidance, float *loss /*dev, 1*/, float *d_e_n /*dev or NULL*/,
+                   float *target /*dev or NULL*/, void *ws /*dev*/, size_t ws_bytes, salun_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

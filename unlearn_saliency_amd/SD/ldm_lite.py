@@ -36,6 +36,7 @@ class LatentDiffusionLite(nn.Module):
                  first_stage=None, cond_stage=None, scale_factor=0.18215, bf16=False):
         super().__init__()
         self.model = _Wrapper(UNetModel(**(unet_config or V1_UNET_CONFIG)))
+        self.unet_config = dict(unet_config or V1_UNET_CONFIG)   # plain attribute: frozen_copy builds the twin from it
         self.num_timesteps = int(timesteps)
         self.first_stage_key, self.cond_stage_key = "jpg", "txt"
         self.first_stage, self.cond_stage, self.scale_factor = first_stage, cond_stage, scale_factor
@@ -53,6 +54,9 @@ class LatentDiffusionLite(nn.Module):
         # "linear" schedule of the LDM code base: linspace(sqrt(start), sqrt(end))**2 in float64 (util.py:24-30)
         betas = np.linspace(linear_start ** 0.5, linear_end ** 0.5, timesteps, dtype=np.float64) ** 2
         ac = np.cumprod(1.0 - betas, axis=0)
+        # the reference's fp32 `alphas_cumprod` buffer, as a host array: the DDIM tables of SD/ddim.py are computed from
+        # it through numpy.  Deliberately NOT a registered buffer: the state_dict is what the scripts save.
+        self.alphas_cumprod_f32 = ac.astype(np.float32)
         self.register_buffer("sqrt_alphas_cumprod", torch.tensor(np.sqrt(ac), dtype=torch.float32))
         self.register_buffer("sqrt_one_minus_alphas_cumprod", torch.tensor(np.sqrt(1.0 - ac), dtype=torch.float32))
 
@@ -93,6 +97,26 @@ class LatentDiffusionLite(nn.Module):
         if n:
             arena.params[z] = ops.fill_normal(arena.n, seed, 0.0, std)[z]
         return n
+
+    def frozen_copy(self) -> "LatentDiffusionLite":
+        """A second model with cloned weights that is never trained: `requires_grad_(False)`, eval mode, on the same
+        kernels as this one.  Its parameters carry `_salun_frozen`, under which weightimg.key() leaves the global
+        parameter epoch out — they are in no optimizer's arena, so nothing writes them through raw pointers, and the
+        optimizer steps on THIS model must not mark the twin's packed weight images stale."""
+        twin = LatentDiffusionLite(self.unet_config, timesteps=self.num_timesteps, first_stage=self.first_stage,
+                                   cond_stage=self.cond_stage, scale_factor=self.scale_factor, bf16=self.bf16)
+        twin.load_state_dict(self.state_dict())
+        twin.alphas_cumprod_f32 = self.alphas_cumprod_f32.copy()
+        twin.frozen_param_count = self.frozen_param_count
+        twin = twin.to(self.device)
+        if any(isinstance(m, nn.Conv2d) and type(m) is not nn.Conv2d for m in self.modules()):
+            if hasattr(self, "mfma_linears"):
+                twin.mfma_linears = self.mfma_linears
+            twin.use_mfma_convs()
+        for p in twin.parameters():
+            p.requires_grad_(False)
+            p._salun_frozen = True
+        return twin.eval()
 
     # ---- the calls the scripts make
     def get_input(self, batch, k=None):

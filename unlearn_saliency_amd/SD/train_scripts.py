@@ -1,9 +1,12 @@
-"""SalUn for Stable Diffusion: the four functions of the reference's SD/train-scripts —
+"""SalUn for Stable Diffusion and the baselines it is compared against: the functions of the reference's
+SD/train-scripts —
 
     generate_mask / generate_nsfw_mask      SD/train-scripts/generate_mask.py:8-108, :111-211
     certain_label                           SD/train-scripts/random_label.py:13-156
     nsfw_removal                            SD/train-scripts/nsfw_removal.py:33-175
     proximal_gradient                       SD/train-scripts/proximal_gradient.py:14-186
+    train_esd                               SD/train-scripts/train-esd.py:129-342
+    gradient_ascent                         SD/train-scripts/gradient_ascent.py:14-121
 
 — with the reference's positional parameters.  Data loaders yield latents + context embeddings
 (ldm_lite.py explains why); `model=` / `*_dl=` keyword arguments inject a prepared model and loaders.
@@ -292,3 +295,217 @@ def nsfw_removal(train_method, alpha, batch_size, epochs, lr, config_path, ckpt_
     if forget_dl is None or remain_dl is None:
         raise ValueError("forget_dl: (latents, nude context, clothed context) batches; remain_dl: (latents, context)")
     return model, _unlearn(model, forget_dl, remain_dl, alpha, epochs, lr, mask_path, train_method)
+
+
+# ----------------------------------------------------------------------------- baselines: gradient ascent, ESD
+def gradient_ascent(class_to_forget, train_method, alpha, batch_size, epochs, lr, config_path, ckpt_path, mask_path,
+                    diffusers_config_path, device, image_size=512, ddim_steps=50, *, model=None, forget_dl=None,
+                    remain_dl=None):
+    """SD/train-scripts/gradient_ascent.py:14-121: loss = -LDM-loss(forget) + alpha * LDM-loss(remain), Adam, the
+    saliency mask of `mask_path` on the gradients.  Forget and remain batches are (latents, context) pairs.  A sibling
+    of `_unlearn`'s loop rather than a switch in it: the reference draws for the FORGET batch first here (:86-92), for
+    the remain batch first there.  Recorded losses are `loss / batch_size`, as the reference appends them (:96).
+    The model is saved by the command line under `ga_name(...)`."""
+    model = model or setup_model(config_path, ckpt_path, device)
+    if forget_dl is None or remain_dl is None:
+        raise ValueError("forget_dl and remain_dl: (latents, context) batches")
+    arena = _unet_arena(model)
+    hostperf.freeze_gc()
+    opt = FusedMaskedAdam(arena, lr=lr)
+    mask_u8 = _trainable_mask(arena, train_method)
+    if mask_path:
+        saliency = arena.pack_mask(torch.load(mask_path, map_location=arena.device, weights_only=False))
+        mask_u8 = saliency if mask_u8 is None else (saliency & mask_u8)
+    opt.set_mask(mask_u8)
+    object.__setattr__(model, "_salun_last_optimizer", opt)
+    model.train()
+    losses = []
+    for epoch in range(epochs):
+        remain_iter = iter(remain_dl)
+        for z_f, c_f in forget_dl:
+            opt.zero_grad()
+            try:
+                z_r, c_r = next(remain_iter)
+            except StopIteration:
+                remain_iter = iter(remain_dl)
+                z_r, c_r = next(remain_iter)
+            draws.next_step()
+            sh_f = draws.shard_of(forget_dl, z_f.shape[0])
+            with draws.scope(sh_f):
+                forget_loss = -model.shared_step({"z": z_f, "c": c_f})[0]
+            sh_r = draws.shard_of(remain_dl, z_r.shape[0])
+            with draws.scope(sh_r):
+                remain_loss = model.shared_step({"z": z_r, "c": c_r})[0]
+            if sh_f.weight != 1.0:
+                forget_loss = forget_loss * sh_f.weight
+            if sh_r.weight != 1.0:
+                remain_loss = remain_loss * sh_r.weight
+            loss = forget_loss + alpha * remain_loss
+            loss.backward()
+            opt.step()
+            losses.append(loss.detach())
+    model.eval()
+    return model, ([float(v) / batch_size for v in torch.stack(losses).cpu()] if losses else [])
+
+
+def ga_name(train_method, alpha, epochs, lr, mask_path) -> str:
+    """gradient_ascent.py:59-63"""
+    return f"compvis-ga{'-mask' if mask_path else ''}-method_{train_method}-alpha_{alpha}-epoch_{epochs}-lr_{lr}"
+
+
+ESD_PROMPT_ALIASES = {   # train-esd.py:184-189
+    "allartist": "Kelly Mckernan, Thomas Kinkade, Ajin Demi Human, Alena Aenami, Tyler Edlin, Kilian Eng",
+    "i2p": "hate, harassment, violence, suffering, humiliation, harm, suicide, sexual, nudity, bodily fluids, blood",
+    "artifact": "ugly, tiling, poorly drawn hands, poorly drawn feet, poorly drawn face, out of frame, mutation, mutated, "
+                "extra limbs, extra legs, extra arms, disfigured, deformed, cross-eye, body out of frame, blurry, bad art, "
+                "bad anatomy, blurred, text, watermark, grainy",
+}
+ESD_TRAIN_METHODS = ("noxattn", "selfattn", "xattn", "full", "notime", "xlayer", "selflayer")
+
+
+def esd_words(prompt: str, seperator=None):
+    """-> (word_print, words): the prompt cleaning of train-esd.py:183-195 (the reference's spelling `seperator`)."""
+    word_print = prompt.replace(" ", "")
+    prompt = ESD_PROMPT_ALIASES.get(prompt, prompt)
+    if seperator is not None:
+        return word_print, [w.strip() for w in prompt.split(seperator)]
+    return word_print, [prompt]
+
+
+def esd_selects(name: str, train_method: str) -> bool:
+    """Is the U-Net parameter `name` handed to the optimizer under `train_method` (train-esd.py:207-236)?"""
+    if train_method == "noxattn":
+        return not (name.startswith("out.") or "attn2" in name or "time_embed" in name)
+    if train_method == "selfattn":
+        return "attn1" in name
+    if train_method == "xattn":
+        return "attn2" in name
+    if train_method == "full":
+        return True
+    if train_method == "notime":
+        return not (name.startswith("out.") or "time_embed" in name)
+    if train_method == "xlayer":
+        return "attn2" in name and ("output_blocks.6." in name or "output_blocks.8." in name)
+    if train_method == "selflayer":
+        return "attn1" in name and ("input_blocks.4." in name or "input_blocks.7." in name)
+    raise ValueError(f"train_method {train_method!r} ({' | '.join(ESD_TRAIN_METHODS)})")
+
+
+def _esd_trainable_mask(arena: FlatArena, train_method: str) -> Optional[torch.Tensor]:
+    """`esd_selects` as a u8 mask over the flat arena (None: everything).  Masked-out elements get no Adam update and
+    keep zero moments — the parameters the reference leaves out of its optimizer."""
+    if train_method == "full":
+        return None
+    m = torch.zeros(arena.n, dtype=torch.uint8, device=arena.device)
+    for name, off, k in zip(arena.names, arena.offsets, arena.numels):
+        if esd_selects(name, train_method):
+            m[off:off + k] = 1
+    return m
+
+
+def esd_name(train_method, lr, mask_path) -> str:
+    """train-esd.py:259-263"""
+    return f"compvis-esd{'-mask' if mask_path else ''}-method_{train_method}-lr_{lr}"
+
+
+def save_history(losses, name, word_print):
+    """train-esd.py:373-378: models/{name}/loss.txt (the values written back to back, as `writelines` does) and the
+    moving-average plot when matplotlib is there."""
+    folder = f"models/{name}"
+    os.makedirs(folder, exist_ok=True)
+    with open(f"{folder}/loss.txt", "w") as f:
+        f.writelines([str(i) for i in losses])
+    try:
+        import matplotlib
+        matplotlib.use("Agg")
+        import matplotlib.pyplot as plt
+        import numpy as np
+    except ImportError:
+        return
+    n = 3
+    ret = np.cumsum(losses, dtype=float)
+    ret[n:] = ret[n:] - ret[:-n]
+    plt.plot(ret[n - 1:] / n, label=f"{word_print}_loss")
+    plt.legend(loc="upper left")
+    plt.title("Average loss in trainings", fontsize=20)
+    plt.xlabel("Data point", fontsize=16)
+    plt.ylabel("Loss value", fontsize=16)
+    plt.savefig(f"{folder}/loss.png")
+    plt.close()
+
+
+def train_esd(prompt, train_method, start_guidance, negative_guidance, iterations, lr, config_path, ckpt_path, mask_path,
+              diffusers_config_path, devices, seperator=None, image_size=512, ddim_steps=50, *, model=None,
+              contexts=None, save=False, trace=None):
+    """Erased Stable Diffusion (SD/train-scripts/train-esd.py:129-342), and with `mask_path` ESD restricted to a
+    saliency mask of generate_mask.  Per iteration, in the reference's order of draws: a word; t_enc ~ randint(ddim_steps);
+    t ~ randint(round(t_enc / S * 1000), round((t_enc + 1) / S * 1000)); a start code; z = the guided DDIM chain of the
+    TRAINED model from the start code down to t_enc (SD/ddim.py: one batched U-Net pass and one K21 launch per step);
+    (e_0, e_p) = ONE batched pass of the frozen copy; e_n = eps(z, t, word) of the trained model;
+    loss = MSE(e_n, e_0 - negative_guidance * (e_p - e_0)) with its gradient in one launch (ops.esd_loss); fused masked
+    Adam over `train_method`'s parameters AND the saliency mask.
+
+    `contexts` maps a prompt string to its (1, 77, ctx) context embedding and must hold "" and every word (the text
+    encoder is out of scope, SD/train-scripts/_common.py).  `devices` is accepted for the reference's signature; both
+    models live on devices[0] — one MI355X holds the two U-Nets many times over, so the reference's second GPU is not
+    needed, and with a batch of one latent there is nothing to shard over more devices (no multi-GPU ESD).
+    `save`: write the reference's loss.txt / periodic checkpoints under
+    models/{esd_name}; `trace`: a list that receives one dict per iteration (word, t_enc, t, DDIM steps taken, z, e_0p).
+    Returns (model, losses)."""
+    from .ddim import DDIMSampler
+    word_print, words = esd_words(prompt, seperator)
+    ddim_eta = 0
+    device = devices[0] if isinstance(devices, (list, tuple)) else devices
+    model = model or setup_model(config_path, ckpt_path, device)
+    device = model.device
+    if contexts is None or "" not in contexts or any(w not in contexts for w in words):
+        raise ValueError('contexts: {prompt: (1, 77, ctx) context embedding} holding "" and every word of the prompt')
+    ctx = {k: contexts[k].to(device).float().contiguous() for k in [""] + words}
+    frozen = model.frozen_copy()
+    sampler = DDIMSampler(model).make_schedule(ddim_steps, ddim_eta)
+    arena = _unet_arena(model)
+    hostperf.freeze_gc()
+    opt = FusedMaskedAdam(arena, lr=lr)
+    mask_u8 = _esd_trainable_mask(arena, train_method)
+    if mask_path:
+        saliency = arena.pack_mask(torch.load(mask_path, map_location=arena.device, weights_only=False))
+        mask_u8 = saliency if mask_u8 is None else (saliency & mask_u8)
+    opt.set_mask(mask_u8)
+    object.__setattr__(model, "_salun_last_optimizer", opt)
+    name = esd_name(train_method, lr, mask_path)
+    model.train()
+    hw = int(image_size / 8)
+    cin = model.model.diffusion_model.in_channels
+    losses = []
+    history = lambda: [float(v) for v in torch.stack(losses).cpu()] if losses else []
+    for i in range(iterations):
+        word = draws.sample_one(words)
+        emb_0, emb_p = ctx[""], ctx[word]
+        opt.zero_grad()
+        draws.next_step()
+        t_enc = int(draws.randint(ddim_steps, 1, device))
+        og_num = round((t_enc / ddim_steps) * 1000)
+        og_num_lim = round(((t_enc + 1) / ddim_steps) * 1000)
+        t = draws.randint_range(og_num, og_num_lim, 1, device).long()
+        start_code = draws.randn((1, cin, hw, hw), device)
+        z = sampler.sample(emb_p, emb_0, start_guidance, start_code, till_T=t_enc)
+        with torch.no_grad():
+            e_0p = frozen.apply_model(torch.cat([z, z]), torch.cat([t, t]), torch.cat([emb_0, emb_p]))
+        e_n = model.apply_model(z, t, emb_p)
+        loss = ops.esd_loss(e_n, e_0p, negative_guidance)
+        loss.backward()
+        opt.step()
+        losses.append(loss.detach())
+        if trace is not None:
+            trace.append(dict(word=word, t_enc=t_enc, t=int(t), steps=sampler.last_steps, z=z.clone(), e_0p=e_0p.clone()))
+        if save:
+            if (i + 1) % 500 == 0 and i + 1 != iterations and i + 1 >= 500:   # train-esd.py:325-326, its `i - 1`
+                os.makedirs(f"models/{name}", exist_ok=True)
+                torch.save(model.state_dict(), f"models/{name}/{name}-epoch_{i - 1}.pt")
+            if i % 100 == 0:
+                save_history(history(), name, word_print)
+    model.eval()
+    out = history()
+    if save:
+        save_history(out, name, word_print)
+    return model, out

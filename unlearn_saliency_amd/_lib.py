@@ -188,6 +188,11 @@ SIGNATURES = {
     "salun_minmax_workspace_bytes": (c_size_t, [c_int64]),
     "salun_minmax": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "salun_images_to_u8": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "salun_ldm_ddim_step": (c_int, [c_void_p, c_void_p, c_int] + [c_double] * 6 + [c_void_p, c_void_p, c_void_p, c_int64,
+                                                                                   c_int64, c_void_p]),
+    "salun_esd_loss_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "salun_esd_loss": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_size_t, c_void_p]),
 }
 
 _lib = None

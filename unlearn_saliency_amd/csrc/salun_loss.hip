@@ -93,6 +93,93 @@ __global__ __launch_bounds__(SALUN_BLOCK) void k_sqerr_final(const double *__res
   if (threadIdx.x == 0) *loss = (float)(tot * coef);
 }
 
+// ------------------------------------------------- K21: ESD objective + gradient
+// target = e_0 - ng * (e_p - e_0); d = e_n - target; d_e_n = (2 / N) * d; partial[segment] = sum d^2 (fp32 squares,
+// folded in fp64 in a fixed order).  One correctly rounded fp32 operation per step (no contraction): `target` and
+// `d_e_n` equal the torch expression bit for bit.  A segment is 1024 consecutive floats of the flat tensors.
+__device__ __forceinline__ float esd_elem(float en, float e0, float ep, float ng, float coef, float &tgt, float &g) {
+  const float diff = ep - e0;
+  const float sc = ng * diff;
+  tgt = e0 - sc;
+  const float d = en - tgt;
+  g = coef * d;
+  return d;
+}
+// One segment of one workgroup: elementwise outputs and the workgroup's fp64 sum of the fp32 squares (valid in thread 0).
+__device__ __forceinline__ double esd_segment(const float *__restrict__ en, const float *__restrict__ e0,
+                                              const float *__restrict__ ep, int64_t n, float ng, float coef,
+                                              float *__restrict__ d_en, float *__restrict__ target, int vec, int64_t w,
+                                              double *lds) {
+  const int64_t j0 = w * SEG + (int64_t)threadIdx.x * 4;
+  float d[4] = {0.f, 0.f, 0.f, 0.f};
+  if (vec && j0 + 3 < n) {
+    const float4 a = *reinterpret_cast<const float4 *>(en + j0);
+    const float4 b = *reinterpret_cast<const float4 *>(e0 + j0);
+    const float4 c = *reinterpret_cast<const float4 *>(ep + j0);
+    float4 t, g;
+    d[0] = esd_elem(a.x, b.x, c.x, ng, coef, t.x, g.x);
+    d[1] = esd_elem(a.y, b.y, c.y, ng, coef, t.y, g.y);
+    d[2] = esd_elem(a.z, b.z, c.z, ng, coef, t.z, g.z);
+    d[3] = esd_elem(a.w, b.w, c.w, ng, coef, t.w, g.w);
+    if (d_en) *reinterpret_cast<float4 *>(d_en + j0) = g;
+    if (target) *reinterpret_cast<float4 *>(target + j0) = t;
+  } else {
+    for (int q = 0; q < 4; ++q)
+      if (j0 + q < n) {
+        float t, g;
+        d[q] = esd_elem(en[j0 + q], e0[j0 + q], ep[j0 + q], ng, coef, t, g);
+        if (d_en) d_en[j0 + q] = g;
+        if (target) target[j0 + q] = t;
+      }
+  }
+  const double sq = ((double)(d[0] * d[0]) + (double)(d[1] * d[1])) + ((double)(d[2] * d[2]) + (double)(d[3] * d[3]));
+  return salun_block_sum(sq, lds);
+}
+// The fold of the segment sums by one workgroup: thread t takes segments t, t + 256, ... in index order, then the fixed
+// block tree; loss = sum / N.
+__device__ __forceinline__ void esd_fold(const double *partial, int64_t segs, double inv_n, float *__restrict__ loss,
+                                         double *lds) {
+  double acc = 0.0;
+  for (int64_t j = threadIdx.x; j < segs; j += SALUN_BLOCK) acc += partial[j];
+  const double tot = salun_block_sum(acc, lds);
+  if (threadIdx.x == 0) *loss = (float)(tot * inv_n);
+}
+__global__ __launch_bounds__(SALUN_BLOCK) void k_esd_partial(const float *__restrict__ en, const float *__restrict__ e0,
+                                                             const float *__restrict__ ep, int64_t n, float ng,
+                                                             float coef, double *__restrict__ partial,
+                                                             float *__restrict__ d_en, float *__restrict__ target,
+                                                             int vec) {
+  __shared__ double lds[4];
+  const int64_t segs = (n + SEG - 1) / SEG;
+  for (int64_t w = blockIdx.x; w < segs; w += gridDim.x) {
+    const double tot = esd_segment(en, e0, ep, n, ng, coef, d_en, target, vec, w, lds);
+    if (threadIdx.x == 0) partial[w] = tot;
+  }
+}
+__global__ __launch_bounds__(SALUN_BLOCK) void k_esd_final(const double *__restrict__ partial, int64_t segs, double inv_n,
+                                                           float *__restrict__ loss) {
+  __shared__ double lds[4];
+  esd_fold(partial, segs, inv_n, loss, lds);
+}
+// Up to ESD_ONE_LAUNCH_SEGS segments (the workload's latents are 16): ONE workgroup walks the segments and folds their
+// sums itself, in the order of the two-launch route, so the loss does not depend on the route.  (`partial` is not
+// __restrict__ here: thread 0 writes it, the barrier publishes it to the workgroup, all threads read it.)
+#define ESD_ONE_LAUNCH_SEGS 64
+__global__ __launch_bounds__(SALUN_BLOCK) void k_esd_single(const float *__restrict__ en, const float *__restrict__ e0,
+                                                            const float *__restrict__ ep, int64_t n, float ng, float coef,
+                                                            double *partial, float *__restrict__ d_en,
+                                                            float *__restrict__ target, int vec, double inv_n,
+                                                            float *__restrict__ loss) {
+  __shared__ double lds[4];
+  const int64_t segs = (n + SEG - 1) / SEG;
+  for (int64_t w = 0; w < segs; ++w) {
+    const double tot = esd_segment(en, e0, ep, n, ng, coef, d_en, target, vec, w, lds);
+    if (threadIdx.x == 0) partial[w] = tot;
+  }
+  __syncthreads();
+  esd_fold(partial, segs, inv_n, loss, lds);
+}
+
 // ------------------------------------------------------------- image batches
 // One lane per output pixel (b, y, x): reads the 3 (C) interleaved source bytes of
 // the cropped/flipped source pixel, writes C planar fp32 values (coalesced per plane).
@@ -205,6 +292,36 @@ SALUN_EXPORT int salun_sqerr_loss(const float *a, const float *b, int64_t B, int
                      (float)(-2.0 * coef), partial, dloss_db, vec);
   SALUN_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_sqerr_final, dim3(1), dim3(SALUN_BLOCK), 0, st, partial, B, segs, coef, loss, per_sample);
+  SALUN_LAUNCH_CHECK();
+  return SALUN_OK;
+}
+
+SALUN_EXPORT size_t salun_esd_loss_workspace_bytes(int64_t B, int64_t chw) {
+  if (B < 1 || chw < 1) return 0;
+  return sizeof(double) * (size_t)((B * chw + SEG - 1) / SEG);
+}
+
+SALUN_EXPORT int salun_esd_loss(const float *e_n, const float *e_0p, int64_t B, int64_t chw, double negative_guidance,
+                                float *loss, float *d_e_n, float *target, void *ws, size_t ws_bytes,
+                                salun_stream_t stream) {
+  if (B < 1 || chw < 1 || !e_n || !e_0p || !loss || !ws) return SALUN_EINVAL;
+  if (ws_bytes < salun_esd_loss_workspace_bytes(B, chw)) return SALUN_ENOSPC;
+  const int64_t n = B * chw, segs = (n + SEG - 1) / SEG;
+  const float *e_0 = e_0p, *e_p = e_0p + n;   // rows [0, B) unconditional, rows [B, 2B) conditional
+  const int vec = salun_aligned16(e_n) && salun_aligned16(e_0) && salun_aligned16(e_p) &&
+                  (!d_e_n || salun_aligned16(d_e_n)) && (!target || salun_aligned16(target));
+  hipStream_t st = salun_hip_stream(stream);
+  double *partial = static_cast<double *>(ws);
+  if (segs <= ESD_ONE_LAUNCH_SEGS) {
+    hipLaunchKernelGGL(k_esd_single, dim3(1), dim3(SALUN_BLOCK), 0, st, e_n, e_0, e_p, n, (float)negative_guidance,
+                       (float)(2.0 / (double)n), partial, d_e_n, target, vec, 1.0 / (double)n, loss);
+    SALUN_LAUNCH_CHECK();
+    return SALUN_OK;
+  }
+  hipLaunchKernelGGL(k_esd_partial, dim3(salun_grid_for(segs, 1)), dim3(SALUN_BLOCK), 0, st, e_n, e_0, e_p, n,
+                     (float)negative_guidance, (float)(2.0 / (double)n), partial, d_e_n, target, vec);
+  SALUN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_esd_final, dim3(1), dim3(SALUN_BLOCK), 0, st, partial, segs, 1.0 / (double)n, loss);
   SALUN_LAUNCH_CHECK();
   return SALUN_OK;
 }

@@ -11,7 +11,18 @@
 //   salun_images_to_u8    inverse data transform + min-max normalisation + *255 + 0.5 -> uint8 HWC, one workgroup per
 //                         image; the image is read once into LDS and reduced there.
 //
-// All four are memory / latency bound; 16-byte loads and stores where the shapes allow.
+// K21: salun_ldm_ddim_step  one reverse step of the LDM DDIM sampler (ldm/models/diffusion/ddim.py, p_sample_ddim) on
+//                         latents: guidance combine over the two halves of ONE batched U-Net output (read in place, no
+//                         chunk copy), x0 estimate, direction term, optional noise.  The five coefficients are fp32 scalars
+//                         the host computed from the DDIM tables; the kernel recomputes none.  Every operation is one
+//                         correctly rounded fp32 operation in the reference's order (this file is built with
+//                         -ffp-contract=off, IEEE division, no fast-math), so the result is bit-comparable with numpy.
+//                         At the workload's size (4 x 64 x 64 = 16,384 elements) the step is bound by launch latency, not
+//                         by bandwidth: what it buys is one launch in place of the ~20 small ones the expression costs in
+//                         torch (cat, chunk, four torch.full, ten elementwise operations) between two U-Net passes, 50
+//                         times per ESD iteration.
+//
+// All of them are memory / latency bound; 16-byte loads and stores where the shapes allow.
 #include "salun_common.h"
 
 namespace {
@@ -265,6 +276,65 @@ __global__ __launch_bounds__(SALUN_BLOCK) void k_images_to_u8(const float *__res
   }
 }
 
+// ------------------------------------------------------------------ K21: LDM DDIM step on latents
+struct LdmCoef {
+  float scale, s1m, sqrt_at, dir, sqrt_aprev, sigma;
+};
+
+__device__ __forceinline__ void ldm_elem(float x, float eu, float ec, float z, int guided, int noisy, const LdmCoef &k,
+                                         float &nxt, float &x0) {
+  float e = ec;
+  if (guided) {
+    const float d = ec - eu;
+    const float sd = k.scale * d;
+    e = eu + sd;
+  }
+  const float se = k.s1m * e;
+  const float num = x - se;
+  x0 = num / k.sqrt_at;
+  const float dir = k.dir * e;
+  const float ax = k.sqrt_aprev * x0;
+  float v = ax + dir;
+  if (noisy) {
+    const float sz = k.sigma * z;
+    v = v + sz;
+  }
+  nxt = v;
+}
+
+// x_prev may alias x: every element is read before it is written, by the same thread.  eu == nullptr: no guidance.
+template <int VEC>
+__global__ __launch_bounds__(SALUN_BLOCK) void k_ldm_ddim_step(const float *x, const float *eu, const float *ec,
+                                                               LdmCoef k, const float *z, float *xp, float *x0,
+                                                               int64_t total) {
+  const int guided = eu != nullptr, noisy = z != nullptr;
+  for (int64_t i = (int64_t)blockIdx.x * SALUN_BLOCK + threadIdx.x; i < total; i += (int64_t)gridDim.x * SALUN_BLOCK) {
+    const int64_t off = i * VEC;
+    float vx[VEC], vu[VEC], vc[VEC], vz[VEC], o[VEC], p[VEC];
+    if (VEC == 4) {
+      *reinterpret_cast<float4 *>(vx) = *reinterpret_cast<const float4 *>(x + off);
+      *reinterpret_cast<float4 *>(vc) = *reinterpret_cast<const float4 *>(ec + off);
+      if (guided) *reinterpret_cast<float4 *>(vu) = *reinterpret_cast<const float4 *>(eu + off);
+      if (noisy) *reinterpret_cast<float4 *>(vz) = *reinterpret_cast<const float4 *>(z + off);
+    } else {
+      vx[0] = x[off];
+      vc[0] = ec[off];
+      if (guided) vu[0] = eu[off];
+      if (noisy) vz[0] = z[off];
+    }
+#pragma unroll
+    for (int j = 0; j < VEC; ++j)
+      ldm_elem(vx[j], guided ? vu[j] : 0.0f, vc[j], noisy ? vz[j] : 0.0f, guided, noisy, k, o[j], p[j]);
+    if (VEC == 4) {
+      *reinterpret_cast<float4 *>(xp + off) = *reinterpret_cast<const float4 *>(o);
+      if (x0) *reinterpret_cast<float4 *>(x0 + off) = *reinterpret_cast<const float4 *>(p);
+    } else {
+      xp[off] = o[0];
+      if (x0) x0[off] = p[0];
+    }
+  }
+}
+
 #define IMAGES_U8_MAX_CHW 16000  // 64000 bytes of LDS for the image + the reduction slots: no dynamic-LDS opt-in needed
 
 int step_grid(int64_t items) {
@@ -306,6 +376,33 @@ SALUN_EXPORT int salun_sampler_step(const float *x_t, const float *eps_cond, con
     hipLaunchKernelGGL(k_sampler_step<1>, dim3(step_grid(B * chw)), dim3(SALUN_BLOCK), 0, st, x_t, eps_cond, eps_null,
                        s1, s, abar, idx_t, idx_next, ancestral, (float)eta, noise, draw, seed, ids, (uint64_t)step,
                        x_next, x0, B, chw);
+  }
+  SALUN_LAUNCH_CHECK();
+  return SALUN_OK;
+}
+
+SALUN_EXPORT int salun_ldm_ddim_step(const float *x, const float *eps2, int guided, double scale, double c_s1m,
+                                     double c_sqrt_at, double c_dir, double c_sqrt_aprev, double c_sigma, const float *z,
+                                     float *x_prev, float *x0_out, int64_t B, int64_t chw, salun_stream_t stream) {
+  if (B < 0 || chw < 0) return SALUN_EINVAL;
+  if (!guided && scale != 1.0) return SALUN_EINVAL;
+  if (c_sigma != 0.0 && !z) return SALUN_EINVAL;
+  if (B == 0 || chw == 0) return SALUN_OK;
+  if (!x || !eps2 || !x_prev) return SALUN_EINVAL;
+  if (c_sigma == 0.0) z = nullptr;  // the reference adds 0 * z there
+  const int64_t n = B * chw;
+  const float *eu = guided ? eps2 : nullptr;       // rows [0, B): unconditional
+  const float *ec = guided ? eps2 + n : eps2;      // rows [B, 2B): conditional
+  const LdmCoef k = {(float)scale, (float)c_s1m, (float)c_sqrt_at, (float)c_dir, (float)c_sqrt_aprev, (float)c_sigma};
+  const int vec = (chw % 4 == 0) && salun_aligned16(x) && salun_aligned16(eps2) && salun_aligned16(x_prev) &&
+                  (!z || salun_aligned16(z)) && (!x0_out || salun_aligned16(x0_out));
+  hipStream_t st = salun_hip_stream(stream);
+  if (vec) {
+    hipLaunchKernelGGL(k_ldm_ddim_step<4>, dim3(step_grid(n / 4)), dim3(SALUN_BLOCK), 0, st, x, eu, ec, k, z, x_prev,
+                       x0_out, n / 4);
+  } else {
+    hipLaunchKernelGGL(k_ldm_ddim_step<1>, dim3(step_grid(n)), dim3(SALUN_BLOCK), 0, st, x, eu, ec, k, z, x_prev, x0_out,
+                       n);
   }
   SALUN_LAUNCH_CHECK();
   return SALUN_OK;

@@ -104,6 +104,23 @@ def randint(high: int, n_local: int, device, shard: Optional[Shard] = None) -> t
     return torch.randint(0, high, (sh.b,), device=device)[sh.lo:sh.hi]
 
 
+def randint_range(low: int, high: int, n: int, device) -> torch.Tensor:
+    """`torch.randint(low, high, (n,), device=device)`: a draw that belongs to no batch (ESD's DDPM timestep)."""
+    return torch.randint(int(low), int(high), (n,), device=device)
+
+
+def randn(shape, device) -> torch.Tensor:
+    """`torch.randn(shape).to(device)`: drawn from the HOST generator and moved, as train-esd.py:283 draws its start
+    code — a seeded run starts every chain from the latents the reference's would start from."""
+    return torch.randn(tuple(shape)).to(device)
+
+
+def sample_one(population):
+    """`random.sample(population, 1)[0]` (train-esd.py:268): Python's generator, seeded by `random.seed`."""
+    import random
+    return random.sample(population, 1)[0]
+
+
 def batch_draw(n_local: int, fn, shard: Optional[Shard] = None) -> torch.Tensor:
     """`fn(n)` draws one value per sample (first dimension n): evaluated for the global batch and sliced."""
     sh = _sliced(shard if shard is not None else _current, n_local)

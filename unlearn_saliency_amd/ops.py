@@ -335,6 +335,46 @@ def mse_loss(target: torch.Tensor, pred: torch.Tensor) -> torch.Tensor:
     return _SqErr.apply(target, pred, 1.0 / target.numel())
 
 
+def esd_loss_raw(e_n: torch.Tensor, e_0p: torch.Tensor, negative_guidance: float, want_grad: bool = True,
+                 want_target: bool = False):
+    """salun_esd_loss (K21): `e_0p` is one batched frozen pass, rows [0, B) = e_0, rows [B, 2B) = e_p.
+    Returns (loss[1], d_e_n or None, target or None)."""
+    L = _lib.lib()
+    B = e_n.shape[0]
+    if e_0p.shape[0] != 2 * B or e_0p.shape[1:] != e_n.shape[1:]:
+        raise ValueError(f"e_0p {tuple(e_0p.shape)} is not the two-fold batch of e_n {tuple(e_n.shape)}")
+    chw = e_n.numel() // B
+    loss = torch.empty(1, dtype=torch.float32, device=e_n.device)
+    d = torch.empty_like(e_n) if want_grad else None
+    tgt = torch.empty_like(e_n) if want_target else None
+    ws = workspace(L.salun_esd_loss_workspace_bytes(c_int64(B), c_int64(chw)), e_n.device)
+    check(L.salun_esd_loss(_dev(e_n, torch.float32, "e_n"), _dev(e_0p, torch.float32, "e_0p"), c_int64(B), c_int64(chw),
+                           c_double(negative_guidance), c_void_p(loss.data_ptr()), _dev(d, torch.float32, "d_e_n", True),
+                           _dev(tgt, torch.float32, "target", True), c_void_p(ws.data_ptr()), c_size_t(ws.numel()),
+                           _stream()), "salun_esd_loss")
+    return loss, d, tgt
+
+
+class _EsdLoss(FastFunction):
+    """mean((e_n - (e_0 - ng * (e_p - e_0)))^2) with the gradient to e_n produced in the same pass."""
+
+    @staticmethod
+    def forward(ctx, e_n, e_0p, negative_guidance):
+        loss, d, _ = esd_loss_raw(e_n.contiguous(), e_0p.contiguous(), negative_guidance)
+        ctx.save_for_backward(d)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (d,) = ctx.saved_tensors
+        return d * grad_out, None, None
+
+
+def esd_loss(e_n: torch.Tensor, e_0p: torch.Tensor, negative_guidance: float) -> torch.Tensor:
+    """nn.MSELoss()(e_n, e_0 - negative_guidance * (e_p - e_0)) of train-esd.py:307-311; only `e_n` gets a gradient."""
+    return _EsdLoss.apply(e_n, e_0p, float(negative_guidance))
+
+
 def dropout(x: torch.Tensor, p: float, key: int, sample_offset: int = 0, out: Optional[torch.Tensor] = None,
             seed_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Counter-based dropout of a (n, ...) fp32 batch whose first sample is global sample `sample_offset`

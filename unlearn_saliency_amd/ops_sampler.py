@@ -95,3 +95,28 @@ def images_to_u8(x: torch.Tensor, rescaled: bool = True, value_range: Optional[t
                                         H * W, 1 if rescaled else 0, _dev(value_range, torch.float32, "value_range", True),
                                         _stream()), "salun_images_to_u8")
     return out
+
+
+def ldm_ddim_step(x: torch.Tensor, eps: torch.Tensor, scale: float, c_s1m: float, c_sqrt_at: float, c_dir: float,
+                  c_sqrt_aprev: float, c_sigma: float = 0.0, z: Optional[torch.Tensor] = None,
+                  out: Optional[torch.Tensor] = None, x0: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One reverse step of the LDM DDIM sampler on latents (K21, salun_ldm_ddim_step).  `eps` with 2B rows is the output
+    of one batched U-Net pass over cat([x, x]) (rows [0, B) unconditional, [B, 2B) conditional, read in place); with B
+    rows it is the no-guidance branch and `scale` must be 1.  The coefficients are the host's fp32 values
+    (SD/ddim.py: DDIMSchedule.coefficients).  `out` defaults to a new tensor (pass `x` for in place)."""
+    B, chw = _rows(x)
+    if eps.shape[0] not in (B, 2 * B) or eps.shape[1:] != x.shape[1:]:
+        raise ValueError(f"eps {tuple(eps.shape)} is neither x {tuple(x.shape)} nor its two-fold batch")
+    guided = B > 0 and eps.shape[0] == 2 * B
+    if out is None:
+        out = torch.empty_like(x)
+    for nm, t in (("z", z), ("out", out), ("x0", x0)):
+        if t is not None and t.shape != x.shape:
+            raise ValueError(f"{nm} {tuple(t.shape)} does not match x {tuple(x.shape)}")
+    f = lambda t, nm: _dev(t, torch.float32, nm, True)
+    check(_lib.lib().salun_ldm_ddim_step(_dev(x, torch.float32, "x"), _dev(eps, torch.float32, "eps"), int(guided),
+                                         c_double(scale), c_double(c_s1m), c_double(c_sqrt_at), c_double(c_dir),
+                                         c_double(c_sqrt_aprev), c_double(c_sigma), f(z, "z"),
+                                         _dev(out, torch.float32, "out"), f(x0, "x0"), c_int64(B), c_int64(chw),
+                                         _stream()), "salun_ldm_ddim_step")
+    return out

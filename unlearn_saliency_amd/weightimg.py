@@ -30,9 +30,12 @@ def key(p: torch.Tensor) -> tuple:
     """What an image of `p` is current with.  The epoch: raw-pointer writes.  `p._version`: torch writes on the parameter
     itself.  The address: a re-homed parameter (a flat arena built later, `.to(device)`).  The flat arena's version:
     torch writes on `arena.params`, or any slice of it, do NOT bump the parameter's own counter — `p.data = view` gave
-    it a separate one (flat.py)."""
+    it a separate one (flat.py).  A parameter marked `_salun_frozen` (SD/ldm_lite.py: frozen_copy) is in no optimizer's
+    arena, so no raw-pointer write reaches it: its key leaves the epoch out, and the steps taken on ANOTHER model do not
+    re-pack its images.  Parameters without the marker keep the key above exactly."""
     flat = getattr(p, "_salun_flat", None)
-    return (PARAM_EPOCH[0], p._version, p.data_ptr(), flat._version if flat is not None else -1)
+    epoch = -1 if getattr(p, "_salun_frozen", False) else PARAM_EPOCH[0]
+    return (epoch, p._version, p.data_ptr(), flat._version if flat is not None else -1)
 
 
 # Launches of the pack kernels so far, per image kind (tests, host profile).  The bf16 one is also the "did anything get

@@ -18,7 +18,9 @@ from fixtures import ddpm_batch, ddpm_small_config, fill_params, flat_params
 
 pytestmark = pytest.mark.gpu
 
-SIZES = [1, 3, 4, 1023, 4096 + 5, 2 ** 20 + 1, 2 ** 23 + 4101]
+# the last: a second grid-stride pass whose first tile has two full sub-vectors, a third with 100 live lanes and a fourth
+# with none, then a 3-element tail
+SIZES = [1, 3, 4, 1023, 4096 + 5, 2 ** 20 + 1, 2 ** 23 + 4101, 2048 * 4096 + 4 * (2 * 256 + 100) + 3]
 B1, B2, EPS, LR = 0.9, 0.999, 1e-8, 2e-4
 MOMENT_TOL = 4.5e-5  # tests/test_ddpm_gpu.py's bound for the Adam moments of a replayed reference run
 STRIDE = 997

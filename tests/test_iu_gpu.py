@@ -18,8 +18,10 @@ pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+def _t(a, offset=0):
+    """`a` on the device; offset 1 puts it one element into its allocation (not 16-byte aligned: the scalar route)."""
+    t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    return torch.cat([t.new_zeros(offset), t])[offset:] if offset else t
 
 
 def _rand(shape, seed):
@@ -106,7 +108,7 @@ def test_recurrence_vs_fp64_host_loop(n):
 
 @pytest.mark.parametrize("masked", [False, True])
 @pytest.mark.parametrize("n", [1_000_003, 1, 4097])
-def test_apply_bit_exact_vs_host(masked, n):
+def test_apply_bit_exact_vs_host(masked, n, offset=0):
     from unlearn_saliency_amd import ops_iu
     p, v, g = _rand(n, 20), _rand(n, 21), _rand(n, 22)
     m = (np.random.default_rng(23).integers(0, 2, n)).astype(np.uint8) if masked else None
@@ -114,10 +116,18 @@ def test_apply_bit_exact_vs_host(masked, n):
     want = (p.astype(np.float64) + alpha * (v.astype(np.float64) - beta * g.astype(np.float64))).astype(np.float32)
     if masked:
         want = np.where(m != 0, want, p)
-    d_p = _t(p.copy())
-    ops_iu.apply(d_p, _t(v), _t(g), torch.tensor([beta, 1.0], dtype=torch.float64, device="cuda"),
-                 None if m is None else _t(m), alpha)
+    d_p = _t(p.copy(), offset)
+    ops_iu.apply(d_p, _t(v, offset), _t(g, offset), torch.tensor([beta, 1.0], dtype=torch.float64, device="cuda"),
+                 None if m is None else _t(m, offset), alpha)
     assert np.array_equal(d_p.cpu().numpy().view(np.uint32), want.view(np.uint32))
+
+
+@pytest.mark.parametrize("offset", [0, 1])
+def test_apply_bit_exact_vs_host_wrap(offset):
+    """The same check once past the streaming kernels' grid-stride wrap (2048 workgroups x 4096-element tiles, then a
+    second pass whose first tile has two full sub-vectors, a third with 100 live lanes and a fourth with none, then a
+    3-element tail), on the float4 route and on the scalar route."""
+    test_apply_bit_exact_vs_host(True, 2048 * 4096 + 4 * (2 * 256 + 100) + 3, offset)
 
 
 def test_apply_unaligned_tail():

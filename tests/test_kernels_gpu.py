@@ -12,6 +12,9 @@ pytestmark = pytest.mark.gpu
 
 N18 = 11_173_962  # ResNet-18 (CIFAR) parameter count, SURVEY.md §0 fact 8
 ND = 38_632_323   # CFG-DDPM U-Net
+# The streaming kernels' grid-stride wrap: 2048 workgroups x 4096-element tiles, then a second pass whose first tile
+# has two full sub-vectors, a third with 100 live lanes and a fourth with none, then a 3-element tail.
+WRAP = 2048 * 4096 + 4 * (2 * 256 + 100) + 3
 
 
 @pytest.fixture(scope="module")
@@ -21,8 +24,10 @@ def ops():
     return _ops
 
 
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+def dev(a, offset=0):
+    """`a` on the device; offset 1 puts it one element into its allocation (not 16-byte aligned: the scalar route)."""
+    t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    return torch.cat([t.new_zeros(offset), t])[offset:] if offset else t
 
 
 def bits(a: np.ndarray) -> np.ndarray:
@@ -82,14 +87,20 @@ def test_dropout_shards_concatenate_to_the_global_batch(ops):
 # --------------------------------------------------------------------------- K1
 @pytest.mark.parametrize("n", [1, 3, 4, 1023, 4099, 1_000_003])
 @pytest.mark.parametrize("scale", [1.0, 0.37])
-def test_saliency_accumulate(ops, oracle_mod, n, scale):
+def test_saliency_accumulate(ops, oracle_mod, n, scale, offset=0):
     acc = oracle_mod.fill_normal(n, 1, 0, 1e-3)
     g = oracle_mod.fill_normal(n, 2, 0, 1e-2)
-    d_acc, d_g = dev(acc), dev(g)
+    d_acc, d_g = dev(acc, offset), dev(g, offset)
     for _ in range(3):
         ops.saliency_accumulate(d_acc, d_g, scale)
         oracle_mod.saliency_accumulate(acc, g, scale)
     assert np.array_equal(bits(d_acc.cpu().numpy()), bits(acc))
+
+
+@pytest.mark.parametrize("offset", [0, 1])
+def test_saliency_accumulate_wrap(ops, oracle_mod, offset):
+    """The same check once past the grid-stride wrap, on the float4 route and on the scalar route."""
+    test_saliency_accumulate(ops, oracle_mod, WRAP, 0.37, offset)
 
 
 def test_saliency_accumulate_device_clip(ops, oracle_mod):
@@ -479,13 +490,13 @@ def _sgd_inputs(oracle_mod, n, seed):
 @pytest.mark.parametrize("wd", [5e-4, 0.0])
 @pytest.mark.parametrize("mu", [0.9, 0.0])
 @pytest.mark.parametrize("masked", [True, False])
-def test_masked_sgd_bit_exact(ops, oracle_mod, n, wd, mu, masked):
+def test_masked_sgd_bit_exact(ops, oracle_mod, n, wd, mu, masked, offset=0):
     p, g, buf, m = _sgd_inputs(oracle_mod, n, 10)
     if not masked:
         m = None
     buf[...] = 0
-    dp, dg, db = dev(p), dev(g), dev(buf)
-    dm = dev(m) if masked else None
+    dp, dg, db = dev(p, offset), dev(g, offset), dev(buf, offset)
+    dm = dev(m, offset) if masked else None
     for step in range(3):
         first = step == 0
         ops.masked_sgd_step(dp, dg, db if mu else None, dm, 0.013, mu, wd, first)
@@ -493,6 +504,12 @@ def test_masked_sgd_bit_exact(ops, oracle_mod, n, wd, mu, masked):
     assert np.array_equal(bits(dp.cpu().numpy()), bits(p))
     if mu:
         assert np.array_equal(bits(db.cpu().numpy()), bits(buf))
+
+
+@pytest.mark.parametrize("offset", [0, 1])
+def test_masked_sgd_bit_exact_wrap(ops, oracle_mod, offset):
+    """The same check once past the grid-stride wrap, on the float4 route and on the scalar route."""
+    test_masked_sgd_bit_exact(ops, oracle_mod, WRAP, 5e-4, 0.9, True, offset)
 
 
 def test_masked_sgd_equals_reference_sequence(ops, oracle_mod):
@@ -534,7 +551,7 @@ def test_masked_sgd_resnet18_size_properties(ops):
 
 
 # --------------------------------------------------------------------------- K5
-@pytest.mark.parametrize("n", [1, 7, 4096, 1_000_003, ND])
+@pytest.mark.parametrize("n", [1, 7, 4096, 1_000_003, WRAP, ND])
 def test_grad_sqnorm(ops, oracle_mod, n):
     g = oracle_mod.fill_normal(n, 31, 0, 1e-2)
     got = float(ops.grad_sqnorm(dev(g)).item())
@@ -547,20 +564,26 @@ def test_grad_sqnorm(ops, oracle_mod, n):
 @pytest.mark.parametrize("n", [1, 6, 4096, 500_001])
 @pytest.mark.parametrize("wd", [0.0, 1e-2])
 @pytest.mark.parametrize("masked", [True, False])
-def test_masked_adam_bit_exact(ops, oracle_mod, n, wd, masked):
+def test_masked_adam_bit_exact(ops, oracle_mod, n, wd, masked, offset=0):
     p = oracle_mod.fill_normal(n, 40, 0, 0.05)
     m1 = np.zeros(n, np.float32)
     v = np.zeros(n, np.float32)
     m = (oracle_mod.fill_u8(n, 43) & 1).astype(np.uint8) if masked else None
-    dp, dm1, dv = dev(p), dev(m1), dev(v)
-    dm = dev(m) if masked else None
+    dp, dm1, dv = dev(p, offset), dev(m1, offset), dev(v, offset)
+    dm = dev(m, offset) if masked else None
     for step in range(1, 4):
         g = oracle_mod.fill_normal(n, 50 + step, 0, 1e-3)
-        ops.masked_adam_step(dp, dev(g), dm1, dv, dm, 1e-4, 0.9, 0.999, 1e-8, wd, step, gscale=0.75)
+        ops.masked_adam_step(dp, dev(g, offset), dm1, dv, dm, 1e-4, 0.9, 0.999, 1e-8, wd, step, gscale=0.75)
         oracle_mod.masked_adam_step(p, g, m1, v, m, 0.75, 1e-4, 0.9, 0.999, 1e-8, wd, step)
     assert np.array_equal(bits(dp.cpu().numpy()), bits(p))
     assert np.array_equal(bits(dm1.cpu().numpy()), bits(m1))
     assert np.array_equal(bits(dv.cpu().numpy()), bits(v))
+
+
+@pytest.mark.parametrize("offset", [0, 1])
+def test_masked_adam_bit_exact_wrap(ops, oracle_mod, offset):
+    """The same check once past the grid-stride wrap, on the float4 route and on the scalar route."""
+    test_masked_adam_bit_exact(ops, oracle_mod, WRAP, 1e-2, True, offset)
 
 
 def test_masked_adam_with_a_device_resident_step_counter(ops, oracle_mod):
@@ -654,7 +677,7 @@ def test_eps_mse_autograd_matches_torch(ops):
 
 
 # --------------------------------------------------------------------------- K7
-@pytest.mark.parametrize("n", [1, 4097, 777_777])
+@pytest.mark.parametrize("n", [1, 4097, 777_777, WRAP])
 def test_fim_square_accumulate(ops, oracle_mod, n):
     F = np.zeros(n, np.float32)
     dF = dev(F)

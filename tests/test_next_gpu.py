@@ -13,6 +13,10 @@ from unlearn_saliency_amd import rng
 
 pytestmark = pytest.mark.gpu
 
+# The streaming kernels' grid-stride wrap: 2048 workgroups x 4096-element tiles, then a second pass whose first tile
+# has two full sub-vectors, a third with 100 live lanes and a fourth with none, then a 3-element tail.
+WRAP = 2048 * 4096 + 4 * (2 * 256 + 100) + 3
+
 
 class ListLoader(list):
     def __init__(self, batches):
@@ -60,7 +64,7 @@ def test_proximal_step_matches_reference_expressions(golden_dir):
         ops.proximal_step(torch.from_numpy(p_init.copy()).cuda(), torch.from_numpy(p0).cuda(), 0)
 
 
-@pytest.mark.parametrize("n,offset", [(1, 0), (1023, 0), (4099, 1), (1_000_003, 0), (11_173_962, 0)])
+@pytest.mark.parametrize("n,offset", [(1, 0), (1023, 0), (4099, 1), (1_000_003, 0), (11_173_962, 0), (WRAP, 1)])
 def test_proximal_step_vs_oracle(oracle_mod, n, offset):
     """bit-exact against the numpy restatement, incl. unaligned views and ragged tails; at N18 also the
     size-independent property: at least `ratio` weights land exactly on theta0, the rest moved by exactly tau."""
@@ -82,7 +86,7 @@ def test_proximal_step_vs_oracle(oracle_mod, n, offset):
     assert np.allclose(np.abs(got[moved] - p[moved]), thr, rtol=1e-5, atol=1e-9)
 
 
-@pytest.mark.parametrize("n,offset", [(5, 0), (4099, 1), (1_000_003, 0)])
+@pytest.mark.parametrize("n,offset", [(5, 0), (4099, 1), (1_000_003, 0), (WRAP, 0), (WRAP, 1)])
 def test_ewc_penalty_grad_vs_oracle(oracle_mod, n, offset):
     from unlearn_saliency_amd import ops
     star = rng.normal(n, 11, 0.0, 0.05)

@@ -13,7 +13,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch
 
-from unlearn_saliency_amd import ops
+from unlearn_saliency_amd import _lib, ops, ops_iu
+from unlearn_saliency_amd.streams import _stream
 
 SIZES = {"n18": 11_173_962, "nd": 38_632_323, "ns": 859_520_964}
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s spec
@@ -60,6 +61,17 @@ def run(n, iters, nk_list=(1, 10)):
         ops.masked_adam_step(p, g, m1, v, m, 1e-4, 0.9, 0.999, 1e-8, 0.0, step[0], sqnorm=sq, max_norm=1.0)
 
     rec("masked_adam(29B)", timeit(adam, iters), 29)
+    shadow = p.clone()
+
+    def adam_ema():  # masked_adam's streams + the shadow read and written
+        step[0] += 1
+        ops.adam_ema_step(p, g, m1, v, shadow, m, 1e-4, 0.9, 0.999, 1e-8, 0.0, 0.9999, step[0], sqnorm=sq, max_norm=1.0)
+
+    rec("adam_ema_step(37B)", timeit(adam_ema, iters), 37)
+    del shadow
+    beta = torch.tensor([0.37, 1.0], dtype=torch.float64, device="cuda")
+    # reads p, v, g0 and the u8 mask, writes p (buf and acc stand in for v and g0)
+    rec("iu_apply(17B)", timeit(lambda: ops_iu.apply(p, buf, acc, beta, m, 1e-3), iters), 17)
     rec("saliency_accumulate(12B)", timeit(lambda: ops.saliency_accumulate(acc, g, 1.0), iters), 12)
     del m1, v
     tmp = torch.zeros(n, device="cuda")
@@ -125,9 +137,18 @@ def run_next(n, iters):
         print(f"  {name:44s} {sec*1e6:10.1f} us  {gbs:8.1f} GB/s  ({gbs/HBM_PEAK_GBS:.3f} of 8 TB/s)", flush=True)
 
     rec("ewc_penalty_grad(20B)", timeit(lambda: ops.ewc_penalty_grad(p, p0, F, g, 10.0), iters), 20)
+    # the two streaming halves of proximal_step on their own, through the C ABI (ops has no wrapper for either):
+    # both read p and p0 and write one vector; a fixed tau keeps the soft-threshold's input distribution steady
+    L, ptr, stream = _lib.lib(), (lambda t: _lib.c_void_p(t.data_ptr())), _stream
+    tau = torch.full((1,), 1e-6, device="cuda")
+    rec("param_diff(12B)", timeit(lambda: _lib.check(L.salun_param_diff(ptr(p), ptr(p0), ptr(scratch), n, stream()),
+                                                     "salun_param_diff"), iters), 12)
+    q = p.clone()
+    rec("soft_threshold_step(12B)", timeit(lambda: _lib.check(L.salun_soft_threshold_step(ptr(q), ptr(p0), ptr(tau), n,
+                                                                                        stream()),
+                                                              "salun_soft_threshold_step"), iters), 12)
     # each call starts from the same fresh p (a re-applied step would rank a vector whose lower quarter already ties at 0,
     # i.e. the top-k's full-scan fallback, not the step the unlearning loop takes): copy outside the timed region
-    q = p.clone()
     tot, reps = 0.0, max(iters // 5, 3)
     for i in range(reps + 1):
         q.copy_(p)

@@ -6,10 +6,10 @@
 //   K17b BN, eval  sum_c u_gamma[c] sum_pq dy_i x^_i + u_beta[c] sum_pq dy_i,   x^ from the running statistics
 //   K17c linear    sum_m dy_i[m] (U x_i + u_b)[m]
 //   K17d the scalar recurrence, one thread, fp64, reading a/b and writing beta on the device
-//   K17e p += alpha (v - beta g_0) (* m), beta read from device memory
+//   K17e p += alpha (v - beta g_0) (* m), beta read from device memory; an op on stream_tiles (salun_stream.h)
 // Every reduction is deterministic: per-workgroup fp64 partials in a fixed order, then a fixed-order finish;
 // no float atomics.  Two launches on the same inputs give bit-identical outputs.
-#include "salun_common.h"
+#include "salun_stream.h"
 
 namespace {
 
@@ -167,53 +167,39 @@ __device__ __forceinline__ float iu_step(float p, float v, float g, double beta,
   return static_cast<float>((double)p + alpha * ((double)v - beta * (double)g));
 }
 
-constexpr int UNROLL = 4;
-constexpr int TILE_VEC = UNROLL * SALUN_BLOCK;
-
 // p <- p + alpha (v - beta g0) where m != 0 (everywhere when m is NULL); masked-out weights are not written
+template <bool MASK>
+struct ApplyOp {
+  float *p;
+  const float *v, *g0;
+  const uint8_t *m;
+  double beta, alpha;
+  struct Vec { float4 p, v, g; uint32_t m; };
+  __device__ void load(Vec &x, int64_t e) const {
+    x.p = ld4(p, e);
+    x.v = ld4(v, e);
+    x.g = ld4(g0, e);
+    if (MASK) x.m = ldm(m, e);
+  }
+  __device__ void vec(Vec &x, int64_t e) const {
+    float4 r = x.p;
+    if (!MASK || mbyte(x.m, 0)) r.x = iu_step(x.p.x, x.v.x, x.g.x, beta, alpha);
+    if (!MASK || mbyte(x.m, 1)) r.y = iu_step(x.p.y, x.v.y, x.g.y, beta, alpha);
+    if (!MASK || mbyte(x.m, 2)) r.z = iu_step(x.p.z, x.v.z, x.g.z, beta, alpha);
+    if (!MASK || mbyte(x.m, 3)) r.w = iu_step(x.p.w, x.v.w, x.g.w, beta, alpha);
+    st4(p, e, r);
+  }
+  __device__ void one(int64_t e) const {
+    if (!MASK || m[e]) p[e] = iu_step(p[e], v[e], g0[e], beta, alpha);
+  }
+};
+
 template <bool VEC, bool MASK>
 __global__ __launch_bounds__(SALUN_BLOCK) void k_apply(float *__restrict__ p, const float *__restrict__ v,
                                                        const float *__restrict__ g0, const double *__restrict__ beta_ptr,
                                                        const uint8_t *__restrict__ m, double alpha, int64_t n) {
-  const double beta = *beta_ptr;
-  if (VEC) {
-    const int64_t nvec = n >> 2;
-    const int64_t ntile = (nvec + TILE_VEC - 1) / TILE_VEC;
-    for (int64_t t = blockIdx.x; t < ntile; t += gridDim.x) {
-      const int64_t base = t * TILE_VEC + threadIdx.x;
-      float4 a[UNROLL], b[UNROLL], c[UNROLL];
-      uchar4 k[UNROLL];
-#pragma unroll
-      for (int u = 0; u < UNROLL; ++u) {
-        const int64_t e = base + u * SALUN_BLOCK;
-        if (e < nvec) {
-          a[u] = reinterpret_cast<const float4 *>(p)[e];
-          b[u] = reinterpret_cast<const float4 *>(v)[e];
-          c[u] = reinterpret_cast<const float4 *>(g0)[e];
-          if (MASK) k[u] = reinterpret_cast<const uchar4 *>(m)[e];
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < UNROLL; ++u) {
-        const int64_t e = base + u * SALUN_BLOCK;
-        if (e < nvec) {
-          float4 r = a[u];
-          if (!MASK || k[u].x) r.x = iu_step(a[u].x, b[u].x, c[u].x, beta, alpha);
-          if (!MASK || k[u].y) r.y = iu_step(a[u].y, b[u].y, c[u].y, beta, alpha);
-          if (!MASK || k[u].z) r.z = iu_step(a[u].z, b[u].z, c[u].z, beta, alpha);
-          if (!MASK || k[u].w) r.w = iu_step(a[u].w, b[u].w, c[u].w, beta, alpha);
-          reinterpret_cast<float4 *>(p)[e] = r;
-        }
-      }
-    }
-    if (blockIdx.x == 0) {
-      const int64_t e = (nvec << 2) + threadIdx.x;
-      if (e < n && (!MASK || m[e])) p[e] = iu_step(p[e], v[e], g0[e], beta, alpha);
-    }
-  } else {
-    for (int64_t e = (int64_t)blockIdx.x * SALUN_BLOCK + threadIdx.x; e < n; e += (int64_t)gridDim.x * SALUN_BLOCK)
-      if (!MASK || m[e]) p[e] = iu_step(p[e], v[e], g0[e], beta, alpha);
-  }
+  ApplyOp<MASK> op{p, v, g0, m, *beta_ptr, alpha};
+  stream_tiles<VEC>(n, op);
 }
 
 int finish(const double *partial, int B, int nb, double *out, hipStream_t st) {
@@ -295,18 +281,10 @@ SALUN_EXPORT int salun_iu_apply(float *p, const float *v, const float *g0, const
   hipStream_t st = salun_hip_stream(stream);
   const bool vec = salun_aligned16(p) && salun_aligned16(v) && salun_aligned16(g0) &&
                    (!mask || salun_aligned4(mask));
-  const int grid = vec ? salun_grid_for((n >> 2), TILE_VEC) : salun_grid_for(n, SALUN_BLOCK);
-  if (vec) {
-    if (mask)
-      hipLaunchKernelGGL((k_apply<true, true>), dim3(grid), dim3(SALUN_BLOCK), 0, st, p, v, g0, beta, mask, alpha, n);
-    else
-      hipLaunchKernelGGL((k_apply<true, false>), dim3(grid), dim3(SALUN_BLOCK), 0, st, p, v, g0, beta, mask, alpha, n);
-  } else {
-    if (mask)
-      hipLaunchKernelGGL((k_apply<false, true>), dim3(grid), dim3(SALUN_BLOCK), 0, st, p, v, g0, beta, mask, alpha, n);
-    else
-      hipLaunchKernelGGL((k_apply<false, false>), dim3(grid), dim3(SALUN_BLOCK), 0, st, p, v, g0, beta, mask, alpha, n);
-  }
-  SALUN_LAUNCH_CHECK();
-  return SALUN_OK;
+  return with_bools(
+      [&](auto M) {
+        return stream_launch(k_apply<true, M.value>, k_apply<false, M.value>, vec, n, SALUN_MAX_GRID, st, p, v, g0, beta,
+                             mask, alpha, n);
+      },
+      mask != nullptr);
 }

@@ -3,39 +3,11 @@
 //   K7 Fisher square-accumulate, K20 masked Adam + EMA shadow in one pass.
 //   gfx950 / CDNA4, compiled with -ffp-contract=off.
 //
-// Streaming shape shared by all of them: 256-thread workgroups (one wave per SIMD),
-// each workgroup walks "tiles" of UNROLL x 256 float4 (= 4096 floats for UNROLL 4)
-// grid-stride; inside a tile lane l of sub-vector u touches float4 index
-// tile*UNROLL*256 + u*256 + l, so every global_load_dwordx4 of a wave covers one
-// contiguous 1 KiB and all UNROLL loads of every stream are issued before the first
-// use (12-16 x 16 B in flight per lane).  The u8 mask travels as one dword per float4.
-#include "salun_common.h"
+// Every kernel here is an op on the streaming shape of salun_stream.h (stream_tiles); the gradient, streamed once,
+// is the only operand read with non-temporal loads.
+#include "salun_stream.h"
 
 namespace {
-
-constexpr int UNROLL = 4;
-constexpr int TILE_VEC = UNROLL * SALUN_BLOCK;  // float4 per tile
-constexpr int TILE_ELEMS = TILE_VEC * 4;        // floats per tile
-
-__device__ __forceinline__ float4 ld4(const float *p, int64_t v) {
-  return reinterpret_cast<const float4 *>(p)[v];
-}
-// Streamed-once operand (the gradient): bypass-friendly non-temporal load.
-__device__ __forceinline__ float4 ld4_nt(const float *p, int64_t v) {
-  const float4 *q = reinterpret_cast<const float4 *>(p) + v;
-  float4 r;
-  r.x = __builtin_nontemporal_load(&q->x);
-  r.y = __builtin_nontemporal_load(&q->y);
-  r.z = __builtin_nontemporal_load(&q->z);
-  r.w = __builtin_nontemporal_load(&q->w);
-  return r;
-}
-__device__ __forceinline__ void st4(float *p, int64_t v, float4 x) {
-  reinterpret_cast<float4 *>(p)[v] = x;
-}
-__device__ __forceinline__ uint32_t ldm(const uint8_t *m, int64_t v) {
-  return reinterpret_cast<const uint32_t *>(m)[v];
-}
 
 // ------------------------------------------------------------------------ K1 ----
 struct AccumArgs {
@@ -49,45 +21,23 @@ struct AccumArgs {
 
 __device__ __forceinline__ float accum_elem(float a, float g, float s) { return a + (g * s); }
 
+struct AccumOp {
+  const AccumArgs &a;
+  const float s;
+  struct Vec { float4 acc, g; };
+  __device__ AccumOp(const AccumArgs &a) : a(a), s(a.sqnorm ? salun_clip_coef(*a.sqnorm, a.max_norm) : a.scale) {}
+  __device__ void load(Vec &x, int64_t v) const { x.acc = ld4(a.acc, v); x.g = ld4_nt(a.g, v); }
+  __device__ void vec(Vec &x, int64_t v) const {
+    st4(a.acc, v, make_float4(accum_elem(x.acc.x, x.g.x, s), accum_elem(x.acc.y, x.g.y, s),
+                              accum_elem(x.acc.z, x.g.z, s), accum_elem(x.acc.w, x.g.w, s)));
+  }
+  __device__ void one(int64_t i) const { a.acc[i] = accum_elem(a.acc[i], a.g[i], s); }
+};
+
 template <bool VEC>
 __global__ __launch_bounds__(SALUN_BLOCK) void k_saliency_accumulate(AccumArgs a) {
-  const float s = a.sqnorm ? salun_clip_coef(*a.sqnorm, a.max_norm) : a.scale;
-  if (VEC) {
-    const int64_t nvec = a.n >> 2;
-    const int64_t ntile = (nvec + TILE_VEC - 1) / TILE_VEC;
-    for (int64_t t = blockIdx.x; t < ntile; t += gridDim.x) {
-      const int64_t base = t * TILE_VEC + threadIdx.x;
-      float4 av[UNROLL], gv[UNROLL];
-#pragma unroll
-      for (int u = 0; u < UNROLL; ++u) {
-        const int64_t v = base + u * SALUN_BLOCK;
-        if (v < nvec) {
-          av[u] = ld4(a.acc, v);
-          gv[u] = ld4_nt(a.g, v);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < UNROLL; ++u) {
-        const int64_t v = base + u * SALUN_BLOCK;
-        if (v < nvec) {
-          float4 r;
-          r.x = accum_elem(av[u].x, gv[u].x, s);
-          r.y = accum_elem(av[u].y, gv[u].y, s);
-          r.z = accum_elem(av[u].z, gv[u].z, s);
-          r.w = accum_elem(av[u].w, gv[u].w, s);
-          st4(a.acc, v, r);
-        }
-      }
-    }
-    if (blockIdx.x == 0) {
-      const int64_t i = (nvec << 2) + threadIdx.x;
-      if (i < a.n) a.acc[i] = accum_elem(a.acc[i], a.g[i], s);
-    }
-  } else {
-    for (int64_t i = (int64_t)blockIdx.x * SALUN_BLOCK + threadIdx.x; i < a.n;
-         i += (int64_t)gridDim.x * SALUN_BLOCK)
-      a.acc[i] = accum_elem(a.acc[i], a.g[i], s);
-  }
+  AccumOp op(a);
+  stream_tiles<VEC>(a.n, op);
 }
 
 // --------------------------------------------------------------------- K3+K4 ----
@@ -117,108 +67,68 @@ __device__ __forceinline__ void sgd_elem(float &p, float g, float &b, bool on, c
 }
 
 template <bool HAS_MASK, bool HAS_WD, bool HAS_MOM>
-__global__ __launch_bounds__(SALUN_BLOCK) void k_masked_sgd_vec(SgdArgs a) {
-  const int64_t nvec = a.n >> 2;
-  const int64_t ntile = (nvec + TILE_VEC - 1) / TILE_VEC;
-  for (int64_t t = blockIdx.x; t < ntile; t += gridDim.x) {
-    const int64_t base = t * TILE_VEC + threadIdx.x;
-    float4 pv[UNROLL], gv[UNROLL], bv[UNROLL];
-    uint32_t mv[UNROLL];
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      const int64_t v = base + u * SALUN_BLOCK;
-      if (v < nvec) {
-        mv[u] = HAS_MASK ? ldm(a.m, v) : 0x01010101u;
-        pv[u] = ld4(a.p, v);
-        gv[u] = ld4_nt(a.g, v);
-        if (HAS_MOM) bv[u] = ld4(a.buf, v);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < UNROLL; ++u) {
-      const int64_t v = base + u * SALUN_BLOCK;
-      if (v < nvec) {
-        const uint32_t mm = mv[u];
-        sgd_elem<HAS_WD, HAS_MOM>(pv[u].x, gv[u].x, bv[u].x, (mm & 0x000000FFu) != 0, a);
-        sgd_elem<HAS_WD, HAS_MOM>(pv[u].y, gv[u].y, bv[u].y, (mm & 0x0000FF00u) != 0, a);
-        sgd_elem<HAS_WD, HAS_MOM>(pv[u].z, gv[u].z, bv[u].z, (mm & 0x00FF0000u) != 0, a);
-        sgd_elem<HAS_WD, HAS_MOM>(pv[u].w, gv[u].w, bv[u].w, (mm & 0xFF000000u) != 0, a);
-        st4(a.p, v, pv[u]);
-        if (HAS_MOM) st4(a.buf, v, bv[u]);
-      }
-    }
+struct SgdOp {
+  const SgdArgs &a;
+  struct Vec { float4 p, g, b; uint32_t m; };
+  __device__ void load(Vec &x, int64_t v) const {
+    x.m = HAS_MASK ? ldm(a.m, v) : 0x01010101u;
+    x.p = ld4(a.p, v);
+    x.g = ld4_nt(a.g, v);
+    if (HAS_MOM) x.b = ld4(a.buf, v);
   }
-  if (blockIdx.x == 0) {  // n % 4 tail
-    const int64_t i = (nvec << 2) + threadIdx.x;
-    if (i < a.n) {
-      float p = a.p[i], b = HAS_MOM ? a.buf[i] : 0.0f;
-      sgd_elem<HAS_WD, HAS_MOM>(p, a.g[i], b, HAS_MASK ? a.m[i] != 0 : true, a);
-      a.p[i] = p;
-      if (HAS_MOM) a.buf[i] = b;
-    }
+  __device__ void vec(Vec &x, int64_t v) const {
+    sgd_elem<HAS_WD, HAS_MOM>(x.p.x, x.g.x, x.b.x, mbyte(x.m, 0), a);
+    sgd_elem<HAS_WD, HAS_MOM>(x.p.y, x.g.y, x.b.y, mbyte(x.m, 1), a);
+    sgd_elem<HAS_WD, HAS_MOM>(x.p.z, x.g.z, x.b.z, mbyte(x.m, 2), a);
+    sgd_elem<HAS_WD, HAS_MOM>(x.p.w, x.g.w, x.b.w, mbyte(x.m, 3), a);
+    st4(a.p, v, x.p);
+    if (HAS_MOM) st4(a.buf, v, x.b);
   }
-}
-
-template <bool HAS_MASK, bool HAS_WD, bool HAS_MOM>
-__global__ __launch_bounds__(SALUN_BLOCK) void k_masked_sgd_scalar(SgdArgs a) {
-  for (int64_t i = (int64_t)blockIdx.x * SALUN_BLOCK + threadIdx.x; i < a.n;
-       i += (int64_t)gridDim.x * SALUN_BLOCK) {
+  __device__ void one(int64_t i) const {
     float p = a.p[i], b = HAS_MOM ? a.buf[i] : 0.0f;
     sgd_elem<HAS_WD, HAS_MOM>(p, a.g[i], b, HAS_MASK ? a.m[i] != 0 : true, a);
     a.p[i] = p;
     if (HAS_MOM) a.buf[i] = b;
   }
+};
+
+template <bool HAS_MASK, bool HAS_WD, bool HAS_MOM>
+__global__ __launch_bounds__(SALUN_BLOCK) void k_masked_sgd_vec(SgdArgs a) {
+  SgdOp<HAS_MASK, HAS_WD, HAS_MOM> op{a};
+  stream_tiles<true>(a.n, op);
 }
 
 template <bool HAS_MASK, bool HAS_WD, bool HAS_MOM>
-int launch_sgd(const SgdArgs &a, bool vec, hipStream_t st) {
-  if (vec) {
-    const int grid = salun_grid_for(a.n, TILE_ELEMS);
-    hipLaunchKernelGGL((k_masked_sgd_vec<HAS_MASK, HAS_WD, HAS_MOM>), dim3(grid), dim3(SALUN_BLOCK), 0, st, a);
-  } else {
-    const int grid = salun_grid_for(a.n, SALUN_BLOCK * 4);
-    hipLaunchKernelGGL((k_masked_sgd_scalar<HAS_MASK, HAS_WD, HAS_MOM>), dim3(grid), dim3(SALUN_BLOCK), 0, st, a);
-  }
-  SALUN_LAUNCH_CHECK();
-  return SALUN_OK;
+__global__ __launch_bounds__(SALUN_BLOCK) void k_masked_sgd_scalar(SgdArgs a) {
+  SgdOp<HAS_MASK, HAS_WD, HAS_MOM> op{a};
+  stream_tiles<false>(a.n, op);
 }
 
 // ------------------------------------------------------------------------ K5 ----
 constexpr int REDUCE_MAX_BLOCKS = 1024;
 
+// Four component accumulators in tile order; the tail and the scalar route add into the first.
+struct SqnormOp {
+  const float *g;
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+  struct Vec { float4 g; };
+  __device__ void load(Vec &x, int64_t v) const { x.g = ld4(g, v); }
+  __device__ void vec(Vec &x, int64_t) {
+    s0 = __builtin_fmaf(x.g.x, x.g.x, s0);
+    s1 = __builtin_fmaf(x.g.y, x.g.y, s1);
+    s2 = __builtin_fmaf(x.g.z, x.g.z, s2);
+    s3 = __builtin_fmaf(x.g.w, x.g.w, s3);
+  }
+  __device__ void one(int64_t i) { s0 = __builtin_fmaf(g[i], g[i], s0); }
+};
+
 __global__ __launch_bounds__(SALUN_BLOCK) void k_sqnorm_partial(const float *__restrict__ g, int64_t n,
                                                                 double *__restrict__ partial, int vec) {
   __shared__ double lds[4];
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  if (vec) {
-    const int64_t nvec = n >> 2;
-    const int64_t ntile = (nvec + TILE_VEC - 1) / TILE_VEC;
-    for (int64_t t = blockIdx.x; t < ntile; t += gridDim.x) {
-      const int64_t base = t * TILE_VEC + threadIdx.x;
-      float4 gv[UNROLL];
-#pragma unroll
-      for (int u = 0; u < UNROLL; ++u) {
-        const int64_t v = base + u * SALUN_BLOCK;
-        gv[u] = (v < nvec) ? ld4(g, v) : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-#pragma unroll
-      for (int u = 0; u < UNROLL; ++u) {
-        s0 = __builtin_fmaf(gv[u].x, gv[u].x, s0);
-        s1 = __builtin_fmaf(gv[u].y, gv[u].y, s1);
-        s2 = __builtin_fmaf(gv[u].z, gv[u].z, s2);
-        s3 = __builtin_fmaf(gv[u].w, gv[u].w, s3);
-      }
-    }
-    if (blockIdx.x == 0) {
-      const int64_t i = (nvec << 2) + threadIdx.x;
-      if (i < n) s0 = __builtin_fmaf(g[i], g[i], s0);
-    }
-  } else {
-    for (int64_t i = (int64_t)blockIdx.x * SALUN_BLOCK + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * SALUN_BLOCK)
-      s0 = __builtin_fmaf(g[i], g[i], s0);
-  }
-  const double tot = salun_block_sum(((double)s0 + (double)s1) + ((double)s2 + (double)s3), lds);
+  SqnormOp op{g};
+  if (vec) stream_tiles<true>(n, op);
+  else stream_tiles<false>(n, op);
+  const double tot = salun_block_sum(((double)op.s0 + (double)op.s1) + ((double)op.s2 + (double)op.s3), lds);
   if (threadIdx.x == 0) partial[blockIdx.x] = tot;
 }
 
@@ -270,81 +180,49 @@ __global__ void k_adam_coefficients(long long *step, double lr, double b1, doubl
   }
 }
 
+template <bool HAS_MASK, bool HAS_WD>
+struct AdamOp {
+  AdamArgs &a;
+  const float s;
+  struct Vec { float4 p, g, m1, v; uint32_t m; };
+  __device__ AdamOp(AdamArgs &a) : a(a), s(a.sqnorm ? salun_clip_coef(*a.sqnorm, a.max_norm) : a.gscale) {
+    if (a.coef) { a.bc2_sqrt = a.coef[0]; a.neg_step_size = a.coef[1]; }
+  }
+  __device__ void load(Vec &x, int64_t v) const {
+    x.m = HAS_MASK ? ldm(a.mask, v) : 0x01010101u;
+    x.p = ld4(a.p, v);
+    x.g = ld4_nt(a.g, v);
+    x.m1 = ld4(a.m1, v);
+    x.v = ld4(a.v, v);
+  }
+  __device__ void vec(Vec &x, int64_t v) const {
+    adam_elem<HAS_WD>(x.p.x, x.g.x, x.m1.x, x.v.x, mbyte(x.m, 0) ? 1.f : 0.f, s, a);
+    adam_elem<HAS_WD>(x.p.y, x.g.y, x.m1.y, x.v.y, mbyte(x.m, 1) ? 1.f : 0.f, s, a);
+    adam_elem<HAS_WD>(x.p.z, x.g.z, x.m1.z, x.v.z, mbyte(x.m, 2) ? 1.f : 0.f, s, a);
+    adam_elem<HAS_WD>(x.p.w, x.g.w, x.m1.w, x.v.w, mbyte(x.m, 3) ? 1.f : 0.f, s, a);
+    st4(a.p, v, x.p);
+    st4(a.m1, v, x.m1);
+    st4(a.v, v, x.v);
+  }
+  __device__ float one(int64_t i) const {  // returns the new p
+    float p = a.p[i], m1 = a.m1[i], v = a.v[i];
+    adam_elem<HAS_WD>(p, a.g[i], m1, v, HAS_MASK ? (a.mask[i] ? 1.f : 0.f) : 1.f, s, a);
+    a.p[i] = p;
+    a.m1[i] = m1;
+    a.v[i] = v;
+    return p;
+  }
+};
+
 template <bool HAS_MASK, bool HAS_WD, bool VEC>
 __global__ __launch_bounds__(SALUN_BLOCK) void k_masked_adam(AdamArgs a) {
-  const float s = a.sqnorm ? salun_clip_coef(*a.sqnorm, a.max_norm) : a.gscale;
-  if (a.coef) { a.bc2_sqrt = a.coef[0]; a.neg_step_size = a.coef[1]; }
-  if (VEC) {
-    const int64_t nvec = a.n >> 2;
-    const int64_t ntile = (nvec + TILE_VEC - 1) / TILE_VEC;
-    for (int64_t t = blockIdx.x; t < ntile; t += gridDim.x) {
-      const int64_t base = t * TILE_VEC + threadIdx.x;
-      float4 pv[UNROLL], gv[UNROLL], mv1[UNROLL], vv[UNROLL];
-      uint32_t mk[UNROLL];
-#pragma unroll
-      for (int u = 0; u < UNROLL; ++u) {
-        const int64_t v = base + u * SALUN_BLOCK;
-        if (v < nvec) {
-          mk[u] = HAS_MASK ? ldm(a.mask, v) : 0x01010101u;
-          pv[u] = ld4(a.p, v);
-          gv[u] = ld4_nt(a.g, v);
-          mv1[u] = ld4(a.m1, v);
-          vv[u] = ld4(a.v, v);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < UNROLL; ++u) {
-        const int64_t v = base + u * SALUN_BLOCK;
-        if (v < nvec) {
-          const uint32_t mm = mk[u];
-          adam_elem<HAS_WD>(pv[u].x, gv[u].x, mv1[u].x, vv[u].x, (mm & 0x000000FFu) ? 1.f : 0.f, s, a);
-          adam_elem<HAS_WD>(pv[u].y, gv[u].y, mv1[u].y, vv[u].y, (mm & 0x0000FF00u) ? 1.f : 0.f, s, a);
-          adam_elem<HAS_WD>(pv[u].z, gv[u].z, mv1[u].z, vv[u].z, (mm & 0x00FF0000u) ? 1.f : 0.f, s, a);
-          adam_elem<HAS_WD>(pv[u].w, gv[u].w, mv1[u].w, vv[u].w, (mm & 0xFF000000u) ? 1.f : 0.f, s, a);
-          st4(a.p, v, pv[u]);
-          st4(a.m1, v, mv1[u]);
-          st4(a.v, v, vv[u]);
-        }
-      }
-    }
-    if (blockIdx.x == 0) {
-      const int64_t i = (nvec << 2) + threadIdx.x;
-      if (i < a.n) {
-        float p = a.p[i], m1 = a.m1[i], v = a.v[i];
-        adam_elem<HAS_WD>(p, a.g[i], m1, v, HAS_MASK ? (a.mask[i] ? 1.f : 0.f) : 1.f, s, a);
-        a.p[i] = p;
-        a.m1[i] = m1;
-        a.v[i] = v;
-      }
-    }
-  } else {
-    for (int64_t i = (int64_t)blockIdx.x * SALUN_BLOCK + threadIdx.x; i < a.n;
-         i += (int64_t)gridDim.x * SALUN_BLOCK) {
-      float p = a.p[i], m1 = a.m1[i], v = a.v[i];
-      adam_elem<HAS_WD>(p, a.g[i], m1, v, HAS_MASK ? (a.mask[i] ? 1.f : 0.f) : 1.f, s, a);
-      a.p[i] = p;
-      a.m1[i] = m1;
-      a.v[i] = v;
-    }
-  }
-}
-
-template <bool HAS_MASK, bool HAS_WD>
-int launch_adam(const AdamArgs &a, bool vec, hipStream_t st) {
-  if (vec) {
-    const int grid = salun_grid_for(a.n, TILE_ELEMS);
-    hipLaunchKernelGGL((k_masked_adam<HAS_MASK, HAS_WD, true>), dim3(grid), dim3(SALUN_BLOCK), 0, st, a);
-  } else {
-    const int grid = salun_grid_for(a.n, SALUN_BLOCK * 4);
-    hipLaunchKernelGGL((k_masked_adam<HAS_MASK, HAS_WD, false>), dim3(grid), dim3(SALUN_BLOCK), 0, st, a);
-  }
-  SALUN_LAUNCH_CHECK();
-  return SALUN_OK;
+  AdamOp<HAS_MASK, HAS_WD> op(a);
+  stream_tiles<VEC>(a.n, op);
 }
 
 // ----------------------------------------------------------------------- K20 ----
 // K5's Adam step with the EMA shadow of the parameters updated in the same pass: the new p never leaves the registers
-// between the two (36 B / element in one launch instead of 28 + 12 in two).  adam_elem is K5's, untouched.
+// between the two (36 B / element in one launch instead of 28 + 12 in two).  The Adam part is K5's op, untouched.
 struct AdamEmaArgs {
   AdamArgs a;
   float *shadow;
@@ -356,136 +234,52 @@ struct AdamEmaArgs {
 // contraction off, so the fma is written out.
 __device__ __forceinline__ float ema_elem(float sh, float p, float w) { return __builtin_fmaf(w, p - sh, sh); }
 
+template <bool HAS_MASK, bool HAS_WD>
+struct AdamEmaOp {
+  AdamOp<HAS_MASK, HAS_WD> adam;
+  float *const shadow;
+  const float w;
+  struct Vec { typename AdamOp<HAS_MASK, HAS_WD>::Vec a; float4 sh; };
+  __device__ AdamEmaOp(AdamEmaArgs &e) : adam(e.a), shadow(e.shadow), w(e.w) {}
+  __device__ void load(Vec &x, int64_t v) const { adam.load(x.a, v); x.sh = ld4(shadow, v); }
+  __device__ void vec(Vec &x, int64_t v) const {
+    adam.vec(x.a, v);
+    st4(shadow, v, make_float4(ema_elem(x.sh.x, x.a.p.x, w), ema_elem(x.sh.y, x.a.p.y, w),
+                               ema_elem(x.sh.z, x.a.p.z, w), ema_elem(x.sh.w, x.a.p.w, w)));
+  }
+  __device__ void one(int64_t i) const { shadow[i] = ema_elem(shadow[i], adam.one(i), w); }
+};
+
 template <bool HAS_MASK, bool HAS_WD, bool VEC>
 __global__ __launch_bounds__(SALUN_BLOCK) void k_adam_ema(AdamEmaArgs e) {
-  AdamArgs &a = e.a;
-  const float s = a.sqnorm ? salun_clip_coef(*a.sqnorm, a.max_norm) : a.gscale;
-  if (a.coef) { a.bc2_sqrt = a.coef[0]; a.neg_step_size = a.coef[1]; }
-  const float w = e.w;
-  if (VEC) {
-    const int64_t nvec = a.n >> 2;
-    const int64_t ntile = (nvec + TILE_VEC - 1) / TILE_VEC;
-    for (int64_t t = blockIdx.x; t < ntile; t += gridDim.x) {
-      const int64_t base = t * TILE_VEC + threadIdx.x;
-      float4 pv[UNROLL], gv[UNROLL], mv1[UNROLL], vv[UNROLL], sv[UNROLL];
-      uint32_t mk[UNROLL];
-#pragma unroll
-      for (int u = 0; u < UNROLL; ++u) {
-        const int64_t v = base + u * SALUN_BLOCK;
-        if (v < nvec) {
-          mk[u] = HAS_MASK ? ldm(a.mask, v) : 0x01010101u;
-          pv[u] = ld4(a.p, v);
-          gv[u] = ld4_nt(a.g, v);
-          mv1[u] = ld4(a.m1, v);
-          vv[u] = ld4(a.v, v);
-          sv[u] = ld4(e.shadow, v);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < UNROLL; ++u) {
-        const int64_t v = base + u * SALUN_BLOCK;
-        if (v < nvec) {
-          const uint32_t mm = mk[u];
-          adam_elem<HAS_WD>(pv[u].x, gv[u].x, mv1[u].x, vv[u].x, (mm & 0x000000FFu) ? 1.f : 0.f, s, a);
-          adam_elem<HAS_WD>(pv[u].y, gv[u].y, mv1[u].y, vv[u].y, (mm & 0x0000FF00u) ? 1.f : 0.f, s, a);
-          adam_elem<HAS_WD>(pv[u].z, gv[u].z, mv1[u].z, vv[u].z, (mm & 0x00FF0000u) ? 1.f : 0.f, s, a);
-          adam_elem<HAS_WD>(pv[u].w, gv[u].w, mv1[u].w, vv[u].w, (mm & 0xFF000000u) ? 1.f : 0.f, s, a);
-          sv[u].x = ema_elem(sv[u].x, pv[u].x, w);
-          sv[u].y = ema_elem(sv[u].y, pv[u].y, w);
-          sv[u].z = ema_elem(sv[u].z, pv[u].z, w);
-          sv[u].w = ema_elem(sv[u].w, pv[u].w, w);
-          st4(a.p, v, pv[u]);
-          st4(a.m1, v, mv1[u]);
-          st4(a.v, v, vv[u]);
-          st4(e.shadow, v, sv[u]);
-        }
-      }
-    }
-    if (blockIdx.x == 0) {
-      const int64_t i = (nvec << 2) + threadIdx.x;
-      if (i < a.n) {
-        float p = a.p[i], m1 = a.m1[i], v = a.v[i];
-        adam_elem<HAS_WD>(p, a.g[i], m1, v, HAS_MASK ? (a.mask[i] ? 1.f : 0.f) : 1.f, s, a);
-        a.p[i] = p;
-        a.m1[i] = m1;
-        a.v[i] = v;
-        e.shadow[i] = ema_elem(e.shadow[i], p, w);
-      }
-    }
-  } else {
-    for (int64_t i = (int64_t)blockIdx.x * SALUN_BLOCK + threadIdx.x; i < a.n;
-         i += (int64_t)gridDim.x * SALUN_BLOCK) {
-      float p = a.p[i], m1 = a.m1[i], v = a.v[i];
-      adam_elem<HAS_WD>(p, a.g[i], m1, v, HAS_MASK ? (a.mask[i] ? 1.f : 0.f) : 1.f, s, a);
-      a.p[i] = p;
-      a.m1[i] = m1;
-      a.v[i] = v;
-      e.shadow[i] = ema_elem(e.shadow[i], p, w);
-    }
-  }
-}
-
-template <bool HAS_MASK, bool HAS_WD>
-int launch_adam_ema(const AdamEmaArgs &e, bool vec, hipStream_t st) {
-  if (vec) {
-    const int grid = salun_grid_for(e.a.n, TILE_ELEMS);
-    hipLaunchKernelGGL((k_adam_ema<HAS_MASK, HAS_WD, true>), dim3(grid), dim3(SALUN_BLOCK), 0, st, e);
-  } else {
-    const int grid = salun_grid_for(e.a.n, SALUN_BLOCK * 4);
-    hipLaunchKernelGGL((k_adam_ema<HAS_MASK, HAS_WD, false>), dim3(grid), dim3(SALUN_BLOCK), 0, st, e);
-  }
-  SALUN_LAUNCH_CHECK();
-  return SALUN_OK;
+  AdamEmaOp<HAS_MASK, HAS_WD> op(e);
+  stream_tiles<VEC>(e.a.n, op);
 }
 
 // ------------------------------------------------------------------------ K7 ----
+// F += tmp^2 / n_data ; tmp <- 0
+struct FimOp {
+  float *F, *tmp;
+  float n_data;
+  struct Vec { float4 f, t; };
+  __device__ static float elem(float f, float t, float n_data) { return f + ((t * t) / n_data); }
+  __device__ void load(Vec &x, int64_t v) const { x.f = ld4(F, v); x.t = ld4(tmp, v); }
+  __device__ void vec(Vec &x, int64_t v) const {
+    st4(F, v, make_float4(elem(x.f.x, x.t.x, n_data), elem(x.f.y, x.t.y, n_data), elem(x.f.z, x.t.z, n_data),
+                          elem(x.f.w, x.t.w, n_data)));
+    st4(tmp, v, make_float4(0.f, 0.f, 0.f, 0.f));
+  }
+  __device__ void one(int64_t i) const {
+    F[i] = elem(F[i], tmp[i], n_data);
+    tmp[i] = 0.f;
+  }
+};
+
 template <bool VEC>
 __global__ __launch_bounds__(SALUN_BLOCK) void k_fim_square_accumulate(float *__restrict__ F, float *__restrict__ tmp,
                                                                         float n_data, int64_t n) {
-  if (VEC) {
-    const int64_t nvec = n >> 2;
-    const int64_t ntile = (nvec + TILE_VEC - 1) / TILE_VEC;
-    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int64_t t = blockIdx.x; t < ntile; t += gridDim.x) {
-      const int64_t base = t * TILE_VEC + threadIdx.x;
-      float4 fv[UNROLL], tv[UNROLL];
-#pragma unroll
-      for (int u = 0; u < UNROLL; ++u) {
-        const int64_t v = base + u * SALUN_BLOCK;
-        if (v < nvec) {
-          fv[u] = ld4(F, v);
-          tv[u] = ld4(tmp, v);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < UNROLL; ++u) {
-        const int64_t v = base + u * SALUN_BLOCK;
-        if (v < nvec) {
-          fv[u].x = fv[u].x + ((tv[u].x * tv[u].x) / n_data);
-          fv[u].y = fv[u].y + ((tv[u].y * tv[u].y) / n_data);
-          fv[u].z = fv[u].z + ((tv[u].z * tv[u].z) / n_data);
-          fv[u].w = fv[u].w + ((tv[u].w * tv[u].w) / n_data);
-          st4(F, v, fv[u]);
-          st4(tmp, v, zero);
-        }
-      }
-    }
-    if (blockIdx.x == 0) {
-      const int64_t i = (nvec << 2) + threadIdx.x;
-      if (i < n) {
-        const float t = tmp[i];
-        F[i] = F[i] + ((t * t) / n_data);
-        tmp[i] = 0.f;
-      }
-    }
-  } else {
-    for (int64_t i = (int64_t)blockIdx.x * SALUN_BLOCK + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * SALUN_BLOCK) {
-      const float t = tmp[i];
-      F[i] = F[i] + ((t * t) / n_data);
-      tmp[i] = 0.f;
-    }
-  }
+  FimOp op{F, tmp, n_data};
+  stream_tiles<VEC>(n, op);
 }
 
 }  // namespace
@@ -496,14 +290,9 @@ SALUN_EXPORT int salun_saliency_accumulate(float *acc, const float *g, double sc
   if (n < 0 || (n > 0 && (!acc || !g))) return SALUN_EINVAL;
   if (n == 0) return SALUN_OK;
   AccumArgs a{acc, g, sqnorm, (float)scale, (float)max_norm, n};
-  hipStream_t st = salun_hip_stream(stream);
-  if (salun_aligned16(acc) && salun_aligned16(g)) {
-    hipLaunchKernelGGL(k_saliency_accumulate<true>, dim3(salun_grid_for(n, TILE_ELEMS)), dim3(SALUN_BLOCK), 0, st, a);
-  } else {
-    hipLaunchKernelGGL(k_saliency_accumulate<false>, dim3(salun_grid_for(n, SALUN_BLOCK * 4)), dim3(SALUN_BLOCK), 0, st, a);
-  }
-  SALUN_LAUNCH_CHECK();
-  return SALUN_OK;
+  const bool vec = salun_aligned16(acc) && salun_aligned16(g);
+  return stream_launch(k_saliency_accumulate<true>, k_saliency_accumulate<false>, vec, n, SALUN_MAX_GRID,
+                       salun_hip_stream(stream), a);
 }
 
 SALUN_EXPORT int salun_masked_sgd_step(float *p, const float *g, float *buf, const uint8_t *m, double lr,
@@ -518,18 +307,12 @@ SALUN_EXPORT int salun_masked_sgd_step(float *p, const float *g, float *buf, con
   const bool vec = salun_aligned16(p) && salun_aligned16(g) && (!has_mom || salun_aligned16(buf)) &&
                    (!has_mask || salun_aligned4(m));
   hipStream_t st = salun_hip_stream(stream);
-#define SALUN_SGD_CASE(M, W, O) \
-  if (has_mask == M && has_wd == W && has_mom == O) return launch_sgd<M, W, O>(a, vec, st);
-  SALUN_SGD_CASE(true, true, true)
-  SALUN_SGD_CASE(true, true, false)
-  SALUN_SGD_CASE(true, false, true)
-  SALUN_SGD_CASE(true, false, false)
-  SALUN_SGD_CASE(false, true, true)
-  SALUN_SGD_CASE(false, true, false)
-  SALUN_SGD_CASE(false, false, true)
-  SALUN_SGD_CASE(false, false, false)
-#undef SALUN_SGD_CASE
-  return SALUN_EINVAL;
+  return with_bools(
+      [&](auto M, auto W, auto O) {
+        return stream_launch(k_masked_sgd_vec<M.value, W.value, O.value>, k_masked_sgd_scalar<M.value, W.value, O.value>,
+                             vec, n, SALUN_MAX_GRID, st, a);
+      },
+      has_mask, has_wd, has_mom);
 }
 
 SALUN_EXPORT size_t salun_reduce_workspace_bytes(int64_t n) {
@@ -544,8 +327,8 @@ SALUN_EXPORT int salun_grad_sqnorm(const float *g, int64_t n, float *out, void *
   hipStream_t st = salun_hip_stream(stream);
   double *partial = static_cast<double *>(ws);
   const int vec = salun_aligned16(g) ? 1 : 0;
-  int grid = salun_grid_for(n, TILE_ELEMS);
-  if (grid > REDUCE_MAX_BLOCKS) grid = REDUCE_MAX_BLOCKS;
+  // one kernel for both routes, sized as the float4 route on both: the returned float depends on the partition
+  const int grid = stream_grid(n, true, REDUCE_MAX_BLOCKS);
   hipLaunchKernelGGL(k_sqnorm_partial, dim3(grid), dim3(SALUN_BLOCK), 0, st, g, n, partial, vec);
   SALUN_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_sum_partials_f32, dim3(1), dim3(SALUN_BLOCK), 0, st, partial, grid, out);
@@ -610,10 +393,12 @@ static int masked_adam_impl(float *p, const float *g, float *m1, float *v, const
   const bool vec = salun_aligned16(p) && salun_aligned16(g) && salun_aligned16(m1) && salun_aligned16(v) &&
                    (!has_mask || salun_aligned4(mask));
   hipStream_t st = salun_hip_stream(stream);
-  if (has_mask && has_wd) return launch_adam<true, true>(a, vec, st);
-  if (has_mask && !has_wd) return launch_adam<true, false>(a, vec, st);
-  if (!has_mask && has_wd) return launch_adam<false, true>(a, vec, st);
-  return launch_adam<false, false>(a, vec, st);
+  return with_bools(
+      [&](auto M, auto W) {
+        return stream_launch(k_masked_adam<M.value, W.value, true>, k_masked_adam<M.value, W.value, false>, vec, n,
+                             SALUN_MAX_GRID, st, a);
+      },
+      has_mask, has_wd);
 }
 
 // K20: the five vectors are read and written by the same lane in one pass, so two of them sharing memory would make
@@ -635,10 +420,12 @@ static int adam_ema_impl(float *p, const float *g, float *m1, float *v, float *s
   const bool vec = salun_aligned16(p) && salun_aligned16(g) && salun_aligned16(m1) && salun_aligned16(v) &&
                    salun_aligned16(shadow) && (!has_mask || salun_aligned4(mask));
   hipStream_t st = salun_hip_stream(stream);
-  if (has_mask && has_wd) return launch_adam_ema<true, true>(e, vec, st);
-  if (has_mask && !has_wd) return launch_adam_ema<true, false>(e, vec, st);
-  if (!has_mask && has_wd) return launch_adam_ema<false, true>(e, vec, st);
-  return launch_adam_ema<false, false>(e, vec, st);
+  return with_bools(
+      [&](auto M, auto W) {
+        return stream_launch(k_adam_ema<M.value, W.value, true>, k_adam_ema<M.value, W.value, false>, vec, n,
+                             SALUN_MAX_GRID, st, e);
+      },
+      has_mask, has_wd);
 }
 
 SALUN_EXPORT int salun_adam_ema_step(float *p, const float *g, float *m1, float *v, float *shadow, const uint8_t *mask,
@@ -663,16 +450,9 @@ SALUN_EXPORT int salun_fim_square_accumulate(float *F, float *tmp, double n_data
                                              salun_stream_t stream) {
   if (n < 0 || n_data == 0.0 || (n > 0 && (!F || !tmp))) return SALUN_EINVAL;
   if (n == 0) return SALUN_OK;
-  hipStream_t st = salun_hip_stream(stream);
-  if (salun_aligned16(F) && salun_aligned16(tmp)) {
-    hipLaunchKernelGGL(k_fim_square_accumulate<true>, dim3(salun_grid_for(n, TILE_ELEMS)), dim3(SALUN_BLOCK), 0, st,
-                       F, tmp, (float)n_data, n);
-  } else {
-    hipLaunchKernelGGL(k_fim_square_accumulate<false>, dim3(salun_grid_for(n, SALUN_BLOCK * 4)), dim3(SALUN_BLOCK), 0,
-                       st, F, tmp, (float)n_data, n);
-  }
-  SALUN_LAUNCH_CHECK();
-  return SALUN_OK;
+  const bool vec = salun_aligned16(F) && salun_aligned16(tmp);
+  return stream_launch(k_fim_square_accumulate<true>, k_fim_square_accumulate<false>, vec, n, SALUN_MAX_GRID,
+                       salun_hip_stream(stream), F, tmp, (float)n_data, n);
 }
 
 

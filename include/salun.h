@@ -814,6 +814,41 @@ int salun_esd_loss(const float *e_n /*dev*/, const float *e_0p /*dev, 2B rows*/,
                    double negative_guidance, float *loss /*dev, 1*/, float *d_e_n /*dev or NULL*/,
                    float *target /*dev or NULL*/, void *ws /*dev*/, size_t ws_bytes, salun_stream_t stream);
 
+/* ----------------------------------------------------------------- K22 --
+ * Global unstructured pruning on the flat arena (csrc/salun_prune.hip).
+ * Replaces  torch.nn.utils.prune.global_unstructured(L1Unstructured | RandomUnstructured)  over every nn.Conv2d weight
+ *   Classification/pruner/utils.py:23-35,66-80  and the per-forward  weight_orig * weight_mask  of its hooks.
+ * p (n floats) is the flat parameter vector, buf (n floats or NULL) the momentum vector, keep (n bytes, 1 = alive) the
+ * prune mask.  segs (dev) holds nseg <= SALUN_PRUNE_MAX_SEGMENTS pairs (off, len) of disjoint ascending element ranges
+ * of total length n_sel: the weights that may be pruned.  The kernels verify the table against n and n_sel before they
+ * touch memory; a refused table changes nothing and is reported by salun_prune_status (error bit 2).
+ * `alive` is the caller's count R of segment elements with keep == 1 (the host tracks it: n_sel at first, minus k_prune
+ * per round); 0 <= k_prune <= alive.
+ *   Among the alive segment elements the k_prune with the smallest |p| get keep = 0, p = 0, buf = 0.  Every other byte
+ *   of p, buf and keep — outside the segments, already pruned, kept — is left bit-identical.  Ties at the threshold
+ *   magnitude are pruned highest flat index first (the complement of K2's rule).  k_prune == 0 launches nothing,
+ *   k_prune == alive prunes every alive element.  An alive weight of exactly 0.0 ranks by its magnitude like any other:
+ *   pruned entries are told apart by keep, not by value, and never return.
+ *   rnd (dev, n_sel floats, or NULL): rank by rnd[j] (j = position in the concatenated segments) instead of |p| — with
+ *   salun_fill_uniform keys, a uniform draw without replacement among the alive weights.
+ *   flags: SALUN_TOPK_FORCE_FULL_SCAN or 0.
+ * Three launches: gather the keys (pruned entries as NaN, which K2 ranks after every number), salun_mask_topk_ex on the
+ * compact keys with k = alive - k_prune, scatter.  Traffic: about 9 B per segment element plus the select's.
+ * salun_prune_status synchronises the stream: `ranked` != 0 reads the select's status (route, error bit 1: its grid
+ * barrier timed out and the round's result is INVALID) — pass it when 0 < k_prune < alive, the rounds that rank. */
+#define SALUN_PRUNE_MAX_SEGMENTS 512
+size_t salun_prune_workspace_bytes(int64_t n_sel);
+int salun_prune_global(float *p /*dev*/, float *buf /*dev or NULL*/, uint8_t *keep /*dev*/, int64_t n,
+                       const int64_t *segs /*dev, 2 * nseg*/, int nseg, int64_t n_sel, int64_t alive, int64_t k_prune,
+                       const float *rnd /*dev or NULL*/, unsigned flags, void *ws /*dev*/, size_t ws_bytes,
+                       salun_stream_t stream);
+int salun_prune_status(const void *ws /*dev*/, int64_t n_sel, int ranked, int *route_out /*host*/,
+                       int *error_out /*host*/, salun_stream_t stream);
+/* *count (dev, 1 int64) = number of exact zeros (+0 or -0) of p inside the segments — check_sparsity's
+ * torch.sum(weight == 0) over the conv layers — or -1 if the table was refused.  One memset and one launch, no sync. */
+int salun_prune_count_zeros(const float *p /*dev*/, int64_t n, const int64_t *segs /*dev, 2 * nseg*/, int nseg,
+                            int64_t n_sel, int64_t *count /*dev*/, salun_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

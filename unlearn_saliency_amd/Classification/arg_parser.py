@@ -2,7 +2,7 @@
 
 Flag names, types and defaults follow the reference's single parser
 (Classification/arg_parser.py:4-145) so existing command lines keep working; flags that
-only steer out-of-scope components (pruning, ImageNet) are accepted and ignored.
+only steer out-of-scope components (the one-shot pruning drivers, ImageNet) are accepted and ignored.
 Additions of this build are grouped at the end (all optional).
 """
 import argparse
@@ -41,7 +41,7 @@ _REFERENCE_FLAGS = [
     ("--decreasing_lr", dict(default="91,136", help="decreasing strategy")),
     ("--no-aug", dict(action="store_true", default=False, help="No augmentation in training dataset")),
     ("--no-l1-epochs", dict(type=int, default=0, help="non l1 epochs")),
-    # pruning (accepted for CLI compatibility; pruning baselines are out of scope)
+    # pruning (read by FT_prune_bi / GA_prune / GA_prune_bi; --prune and --rewind_pth are accepted only)
     ("--prune", dict(type=str, default="omp")),
     ("--pruning_times", dict(type=int, default=1)),
     ("--rate", dict(type=float, default=0.95)),

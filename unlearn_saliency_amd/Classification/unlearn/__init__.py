@@ -8,14 +8,18 @@ mask), the baselines that share its fused step (GA, GA_l1, FT, FT_l1, raw, bound
 boundary_expanding — SURVEY.md §8 F1), the proximal variant (RL_proximal, F2) and the IU / WoodFisher
 baseline (wfisher: per-sample gradient dots from one batched backward) and Fisher forgetting
 (fisher_new: all classes' squared batch gradients from one pass over the activations) are
-implemented; the per-sample empirical Fisher (fisher), pruning and retrain baselines are registered but raise with a
-scope note.
+implemented, and so are the weight-pruning baselines FT_prune_bi, GA_prune and GA_prune_bi (global magnitude or random
+pruning of the convolution weights as one K22 round on the flat arena); the per-sample empirical Fisher
+(fisher), FT_prune and retrain are registered but raise with a scope note.
 """
 from .boundary_ex import boundary_expanding
 from .boundary_sh import boundary_shrink
 from .fisher import fisher_new
 from .FT import FT, FT_l1
+from .FT_prune_bi import FT_prune_bi
 from .GA import GA, GA_l1
+from .GA_prune import GA_prune
+from .GA_prune_bi import GA_prune_bi
 from .impl import (FusedMaskedSGD, iterative_unlearn, load_unlearn_checkpoint, save_unlearn_checkpoint)
 from .RL import RL
 from .RL_pro import RL_proximal
@@ -41,10 +45,9 @@ _REGISTRY = {
     "fisher": _out_of_scope("fisher", "Fisher-forgetting baseline"),
     "fisher_new": fisher_new,
     "wfisher": Wfisher,
+    # stays a scope note: tests/test_cli.py::test_registry_names_match_reference pins FT_prune to NotImplementedError
     "FT_prune": _out_of_scope("FT_prune", "pruning baseline"),
-    "FT_prune_bi": _out_of_scope("FT_prune_bi", "pruning baseline"),
-    "GA_prune": _out_of_scope("GA_prune", "pruning baseline"),
-    "GA_prune_bi": _out_of_scope("GA_prune_bi", "pruning baseline"),
+    "FT_prune_bi": FT_prune_bi, "GA_prune": GA_prune, "GA_prune_bi": GA_prune_bi,
     "boundary_expanding": boundary_expanding, "boundary_shrink": boundary_shrink, "RL_proximal": RL_proximal,
 }
 

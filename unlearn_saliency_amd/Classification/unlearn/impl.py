@@ -50,11 +50,16 @@ def save_unlearn_checkpoint(model, evaluation_result, args):
 
 
 def load_unlearn_checkpoint(model, device, args):
-    """-> (model, evaluation_result) or None.  (The reference also re-applies torch.nn.utils.prune
-    masks found in the checkpoint, impl.py:38-40 — pruning is out of scope)"""
+    """-> (model, evaluation_result) or None.  A checkpoint of a pruned model (`<conv>.weight_orig` / `.weight_mask`,
+    as the pruning baselines save it) gets its masks re-applied first, as the reference does (impl.py:38-40)."""
     ckpt = utils.load_checkpoint(device, args.save_dir, args.unlearn)
     if ckpt is None or ckpt.get("state_dict") is None:
         return None
+    from .. import pruner
+    current_mask = pruner.extract_mask(ckpt["state_dict"])
+    if current_mask:
+        pruner.prune_model_custom(model, current_mask)
+        pruner.check_sparsity(model)
     model.load_state_dict(ckpt["state_dict"])
     return model, ckpt.get("evaluation_result")
 

@@ -193,6 +193,11 @@ SIGNATURES = {
     "salun_esd_loss_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "salun_esd_loss": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_size_t, c_void_p]),
+    "salun_prune_workspace_bytes": (c_size_t, [c_int64]),
+    "salun_prune_global": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int64, c_int64, c_int64,
+                                   c_void_p, ctypes.c_uint, c_void_p, c_size_t, c_void_p]),
+    "salun_prune_status": (c_int, [c_void_p, c_int64, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_void_p]),
+    "salun_prune_count_zeros": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int64, c_void_p, c_void_p]),
 }
 
 _lib = None

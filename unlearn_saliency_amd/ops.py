@@ -1068,3 +1068,62 @@ def fill_u8(n: int, seed: int, device="cuda") -> torch.Tensor:
     out = torch.empty(n, dtype=torch.uint8, device=device)
     check(_lib.lib().salun_fill_u8(c_void_p(out.data_ptr()), c_int64(n), c_uint64(seed), _stream()), "salun_fill_u8")
     return out
+
+
+# ----------------------------------------------------------------------------- K22
+def prune_amount(amount: float, alive: int) -> int:
+    """How many of `alive` weights a round at float `amount` prunes: torch.nn.utils.prune's `round(amount * n)`
+    (Python round: half to even) of the REMAINING weights, which is how global_unstructured reads a float amount on an
+    already pruned model.  0 leaves the mask alone."""
+    if not 0.0 <= float(amount) <= 1.0:
+        raise ValueError(f"amount should be a float in the range [0, 1], got {amount}")
+    return int(round(float(amount) * int(alive)))
+
+
+def prune_global(p: torch.Tensor, buf: Optional[torch.Tensor], keep: torch.Tensor, segs: torch.Tensor, n_sel: int,
+                 alive: int, k_prune: int, rnd: Optional[torch.Tensor] = None, flags: int = 0,
+                 check: bool = True) -> None:
+    """Clear `keep` (and zero `p`, `buf`) at the `k_prune` smallest |p| — or smallest `rnd` keys — among the `alive`
+    elements of the segments with keep == 1; ties: highest flat index first.  `segs`: int64 device tensor (nseg, 2) of
+    (offset, length).  `check=True` reads the select's status once per round (ONE host sync) and raises `TopkFailed`
+    instead of leaving an invalid mask with the optimizer."""
+    L = _lib.lib()
+    n, nseg = p.numel(), segs.shape[0]
+    assert keep.numel() == n and (buf is None or buf.numel() == n) and segs.dim() == 2 and segs.shape[1] == 2
+    assert rnd is None or rnd.numel() == n_sel
+    if k_prune == 0:
+        return
+    weightimg.params_written()
+    ws = workspace(L.salun_prune_workspace_bytes(c_int64(n_sel)), p.device, "prune")
+    _lib.check(L.salun_prune_global(_dev(p, torch.float32, "p"), _dev(buf, torch.float32, "buf", True),
+                                    _dev(keep, torch.uint8, "keep"), c_int64(n), _dev(segs, torch.int64, "segs"),
+                                    c_int(nseg), c_int64(n_sel), c_int64(alive), c_int64(k_prune),
+                                    _dev(rnd, torch.float32, "rnd", True), ctypes.c_uint(flags),
+                                    c_void_p(ws.data_ptr()), c_size_t(ws.numel()), _stream()), "salun_prune_global")
+    if check:
+        route, err = prune_status(p.device, n_sel, ranked=0 < k_prune < alive)
+        if err & 2:   # the select still ran (the host cannot know before it synchronises); its route / status mean nothing
+            raise TopkFailed("salun_prune_global: the kernels refused the segment table (not ascending and disjoint, "
+                             "outside [0, n), or not n_sel elements in all); nothing was changed")
+        if err:
+            raise TopkFailed(f"salun_prune_global: the select's grid barrier timed out (route {route}); the round's "
+                             "result is invalid")
+
+
+def prune_status(device: torch.device, n_sel: int, ranked: bool = True) -> tuple[int, int]:
+    """(route, error bits) of the LAST prune_global call on this device and stream.  Synchronises the stream."""
+    L = _lib.lib()
+    ws = workspace(L.salun_prune_workspace_bytes(c_int64(n_sel)), device, "prune")
+    route, err = c_int(0), c_int(0)
+    check(L.salun_prune_status(c_void_p(ws.data_ptr()), c_int64(n_sel), c_int(int(ranked)), ctypes.byref(route),
+                               ctypes.byref(err), _stream()), "salun_prune_status")
+    return route.value, err.value
+
+
+def prune_count_zeros(p: torch.Tensor, segs: torch.Tensor, n_sel: int) -> torch.Tensor:
+    """Number of exact zeros of `p` inside the segments, as a 1-element int64 device tensor (no host sync)."""
+    out = torch.empty(1, dtype=torch.int64, device=p.device)
+    check(_lib.lib().salun_prune_count_zeros(_dev(p, torch.float32, "p"), c_int64(p.numel()),
+                                             _dev(segs, torch.int64, "segs"), c_int(segs.shape[0]), c_int64(n_sel),
+                                             c_void_p(out.data_ptr()), _stream()), "salun_prune_count_zeros")
+    return out

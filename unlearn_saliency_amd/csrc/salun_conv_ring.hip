@@ -633,6 +633,7 @@ int ring_launch(RingArgs a, int W, bool epi, int wgs_per_cu, hipStream_t st) {
   a.ntiles = ptiles * a.ntile_k;
   a.nchunk = a.Cred / RCC;
   const int IRS = (W == 4 && a.NI > 1) ? 12 : a.TP + 2;  // rows per image in LDS (the kernel's IRS)
+  if (IRS < a.TP + 2) return SALUN_EINVAL;  // 4-wide images taller than 10 rows do not fit the fixed 12-row spacing
   const int PSZ = a.NI * IRS * W;
   const int npiece = RCC * PSZ / 4;
   if (npiece > 12 * 64) return SALUN_EINVAL;  // NPW = 3 units per wave

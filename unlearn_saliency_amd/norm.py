@@ -37,7 +37,7 @@ class _FusedBN(FastFunction):
         gw, gb = gradsink.sink(ctx.params[0]), gradsink.sink(ctx.params[1])
         if gw is None or gb is None:
             gw = gb = None
-        dx, dres, dgamma, dbeta = ops.bn_backward(dy.contiguous(), y, x, weight, mean, invstd, training, relu,
+        dx, dres, dgamma, dbeta = ops.bn_backward(_grad_on_grid(dy), y, x, weight, mean, invstd, training, relu,
                                                   has_res and ctx.needs_input_grad[3], gw, gb)
         if gw is not None:
             gradsink.arrived(weight)
@@ -46,13 +46,29 @@ class _FusedBN(FastFunction):
         return dx, dgamma, dbeta, dres, None, None, None, None, None, None, None
 
 
+def _on_grid(t: torch.Tensor) -> bool:
+    """The kernels load float4: a contiguous tensor whose base is off the 16-byte grid (a slice of a flat buffer) is
+    outside their domain.  Such an input takes the library path like any other shape outside it; a silent aligned copy
+    would add a pass over the activation and an allocation to every call without a trace."""
+    return t.data_ptr() % 16 == 0
+
+
+def _grad_on_grid(dy: torch.Tensor) -> torch.Tensor:
+    """The incoming gradient, contiguous and 16-byte aligned: autograd hands the backward whatever the consumer produced
+    (a slice of a flat buffer among others), and the node cannot step aside any more, so here a copy is the way."""
+    dy = dy.contiguous()
+    return dy if _on_grid(dy) else dy.clone()
+
+
 def _eligible(x: torch.Tensor, bn: nn.BatchNorm2d) -> bool:
     return (type(bn) is nn.BatchNorm2d and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and (x.shape[2] * x.shape[3]) % 4 == 0
             and bn.affine and bn.track_running_stats and bn.momentum is not None and not torch.is_autocast_enabled())
 
 
 def fused_bn_act(x: torch.Tensor, bn: nn.BatchNorm2d, residual: torch.Tensor = None, relu: bool = True):
-    if not _eligible(x, bn):
+    ok = _eligible(x, bn) and (not x.is_contiguous() or _on_grid(x)) and \
+        (residual is None or not residual.is_contiguous() or _on_grid(residual))   # a copy made below is aligned
+    if not ok:
         y = bn(x)
         if residual is not None:
             y = y + residual
@@ -83,7 +99,7 @@ class _FusedGN(FastFunction):
         gw, gb = gradsink.sink(ctx.params[0]), gradsink.sink(ctx.params[1])
         if gw is None or gb is None:
             gw = gb = None
-        dx, dgamma, dbeta = ops.gn_backward(dz.contiguous(), x, weight, bias, mean, rstd, groups, silu, gw, gb)
+        dx, dgamma, dbeta = ops.gn_backward(_grad_on_grid(dz), x, weight, bias, mean, rstd, groups, silu, gw, gb)
         if gw is not None:
             dgamma = dbeta = None
         return dx, dgamma, dbeta, None, None, None
@@ -131,7 +147,7 @@ def enable_fused_gn(flag: bool) -> None:
 
 def fused_gn_act(x: torch.Tensor, gn: nn.GroupNorm, silu: bool = True) -> torch.Tensor:
     """`[x * sigmoid(x)](gn(x))` — one forward and two backward launches on csrc/salun_norm.hip for fp32 NCHW device
-    tensors whose H*W is a power of two; anything else runs the library ops."""
+    tensors whose H*W is a power of two and whose base is 16-byte aligned; anything else runs the library ops."""
     hw = x.shape[2] * x.shape[3] if x.dim() == 4 else 0
     if (_FUSED_GN and type(gn) in _GN_TYPES and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4 and gn.affine
             and x.shape[1] % 8 == 0 and gn.weight.dtype == torch.float32):
@@ -139,7 +155,8 @@ def fused_gn_act(x: torch.Tensor, gn: nn.GroupNorm, silu: bool = True) -> torch.
     if (_FUSED_GN and type(gn) in _GN_TYPES and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
             and gn.affine and hw >= 4 and (hw & (hw - 1)) == 0 and x.shape[1] // gn.num_groups <= 256
             and not torch.is_autocast_enabled()):
-        return _FusedGN.apply(x.contiguous(), gn.weight, gn.bias, gn.num_groups, gn.eps, silu)
+        if not x.is_contiguous() or _on_grid(x):     # a copy is aligned
+            return _FusedGN.apply(x.contiguous(), gn.weight, gn.bias, gn.num_groups, gn.eps, silu)
     y = gn(x)
     return y * torch.sigmoid(y) if silu else y
 

@@ -315,6 +315,28 @@ int salun_conv2d_backward_weight(const float *x /*dev*/, const float *dy /*dev*/
 int salun_conv2d_backward_weight_ex(const float *x /*dev*/, const float *dy /*dev*/, float *dw /*dev*/, int N, int C,
                                     int H, int W, int K, int R, int stride, int pad, int P, int Q, int accumulate,
                                     unsigned flags, void *ws /*dev*/, size_t ws_bytes, salun_stream_t stream);
+/* Which kernel a call of this family runs: the label of the plan the matching entry point would execute, written to
+ * `buf` (NUL-terminated; SALUN_ENOSPC if it does not fit), from the very plan functions the entry points launch from.
+ * Touches no device.  Returns SALUN_OK, or what the entry point would return for the shape (SALUN_EINVAL: refused).
+ *   direction  SALUN_ROUTE_FORWARD (salun_conv2d_forward_fused), SALUN_ROUTE_BACKWARD_DATA (salun_conv2d_backward_data_ws)
+ *              or SALUN_ROUTE_BACKWARD_WEIGHT (salun_conv2d_backward_weight_ex)
+ *   flags      what a plan needs beyond the shape: SALUN_ROUTE_EPI (nbias or addend given), SALUN_ROUTE_W_UNALIGNED (w),
+ *              SALUN_ROUTE_OUT_UNALIGNED (y / dx, the addend or the workspace), SALUN_ROUTE_IN_UNALIGNED (x or dy of
+ *              backward-weight) - off a 16-byte boundary; SALUN_WGRAD_SHARED as for salun_conv2d_backward_weight_ex
+ *   ws_bytes   of the workspace the call would pass (0: none)
+ *   nsplit     (optional) backward-weight: the partial images the reduce kernel adds; else 0
+ * Labels: igemm<R,stride[,dgrad]>/<tile>/<fast|slow>/S<split>[/hw-declined][/epi], dgrad_s2<R,pad<p>>/<tile>,
+ * dgrad_tap[<RH,RW>/<tile>[/P3] ...][/empty], wgrad_1x1<s>, wgrad_smallc<R,s>, wgrad_ring<W<w>>, wgrad_v<s,nit>,
+ * wgrad<R,s,fullC>; <tile> = 256/PT2, 128/KT<n>, 64/KT<n>WK2. */
+#define SALUN_ROUTE_FORWARD 0
+#define SALUN_ROUTE_BACKWARD_DATA 1
+#define SALUN_ROUTE_BACKWARD_WEIGHT 2
+#define SALUN_ROUTE_EPI 2u
+#define SALUN_ROUTE_W_UNALIGNED 4u
+#define SALUN_ROUTE_OUT_UNALIGNED 8u
+#define SALUN_ROUTE_IN_UNALIGNED 16u
+int salun_conv2d_route(int direction, int N, int C, int H, int W, int K, int R, int stride, int pad, int P, int Q,
+                       unsigned flags, size_t ws_bytes, char *buf, size_t buflen, int *nsplit /*or NULL*/);
 
 /* ------------------------------------------------------------------ K8r --
  * 3x3 / stride 1 / pad 1 fp32 convolution, forward and backward-data, with both operands fed by LDS-DMA into a

@@ -185,7 +185,7 @@ def impulses(shape):
 # (N, C, H, W, K, R, stride, pad); the route each was chosen for (conv_routes.py names what it actually gets; every
 # case runs forward, backward-data and backward-weight wherever the library takes the shape)
 CASES = [Case(*s) for s in [
-    # launch_igemm: 64-pixel tile, unsplit, H != W
+    # plan_data: 64-pixel tile, unsplit, H != W
     (3, 8, 8, 16, 16, 3, 1, 1), (3, 8, 16, 8, 16, 3, 1, 1), (2, 8, 4, 32, 16, 3, 1, 1), (2, 8, 2, 64, 16, 3, 1, 1),
     # several images per tile, ragged N
     (5, 8, 2, 2, 8, 3, 1, 1), (5, 64, 4, 4, 64, 3, 1, 1), (3, 64, 8, 4, 16, 3, 1, 1),

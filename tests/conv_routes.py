@@ -1,8 +1,9 @@
-"""Which kernel the fp32 convolution family picks for a shape: a pure-Python mirror of the host-side choices of
-csrc/salun_conv.hip (make_geom, launch_igemm, igemm_split, launch_dgrad / launch_dgrad_s2_merged, the backward-weight
-chain) and of ring_launch's domain in csrc/salun_conv_ring.hip.  It exists so that test_conv_ref_cpu.py can show that
-conv_ref_cpu.CASES reaches every variant, and so that test_conv_exact_gpu.py knows which calls the library must refuse;
-it is checked against the library's own host-side queries there.  A route is a label; None means SALUN_EINVAL.
+"""Which kernel the fp32 convolution family picks for a shape: a pure-Python mirror of the host-side plans of
+csrc/salun_conv.hip (make_geom, pick_tile / pick_tile_s2, plan_data with igemm_split, plan_dgrad_s2, plan_wgrad with
+salun_ring_wgrad_fits) and of ring_launch's domain in csrc/salun_conv_ring.hip.  It exists so that test_conv_ref_cpu.py
+can show that conv_ref_cpu.CASES reaches every variant, and so that test_conv_exact_gpu.py knows which calls the library
+must refuse; test_conv_ref_cpu.py holds it, label for label, to salun_conv2d_route, which prints the plan the library
+launches from, and to the library's workspace queries.  A route is a label; None means SALUN_EINVAL.
 Shapes are conv_ref_cpu.Case: (N, C, H, W, K, R, stride, pad) with P, Q."""
 from collections import namedtuple
 
@@ -15,7 +16,7 @@ def _cdiv(a, b):
 
 
 def geom(N, P, Q, pixt, cs, RH, RW=None):
-    """make_geom / make_geom_rect: tiles of `pixt` output pixels; None outside the domain."""
+    """make_geom: tiles of `pixt` output pixels; None outside the domain."""
     if Q <= 0 or Q & (Q - 1) or Q > pixt:
         return None
     PQ = P * Q
@@ -59,8 +60,9 @@ def igemm_split(wgs, xC, chunk, out_elems, HW):
     return max(S, 1)
 
 
-def igemm(N, xC, yC, yH, yW, R, stride, dgrad, wC, epi=False, ws=False, w_al=True):
-    """launch_igemm<R, stride, dgrad>: forward, or stride-1 backward-data (stride = 1, x = dy)."""
+def igemm(N, xC, yC, yH, yW, R, stride, dgrad, wC, epi=False, ws=False, w_al=True, al=True):
+    """plan_data: forward, or stride-1 backward-data (stride = 1, x = dy).  `al`: the output, the addend and the
+    workspace on 16-byte boundaries (the finishing kernel of a split launch moves float4)."""
     g, pixt = _pick(N, yH, yW, _cdiv(yC, 128), 384, 1 if dgrad else stride, R)
     if g is None:
         return None
@@ -77,7 +79,7 @@ def igemm(N, xC, yC, yH, yW, R, stride, dgrad, wC, epi=False, ws=False, w_al=Tru
             return f"{head}/256/PT2/fast/S1"
     S, note, wgs = 1, "", g.nt * _cdiv(yC, KB)
     if fast and can_split:
-        if ws:
+        if ws and al:
             S = igemm_split(wgs, xC, CC, N * yC * yH * yW, yH * yW)
         if wgs <= 256 and (yH * yW) % 4:
             note = "/hw-declined"
@@ -93,8 +95,8 @@ def data_ws_bytes(N, outC, outH, outW, R, cs):
     return 0 if wgs > 256 else 8 * N * outC * outH * outW * 4
 
 
-def forward(c, epi=False, ws=False, w_al=True):
-    return igemm(c.N, c.C, c.K, c.P, c.Q, c.R, c.stride, False, c.C, epi, ws, w_al)
+def forward(c, epi=False, ws=False, w_al=True, al=True):
+    return igemm(c.N, c.C, c.K, c.P, c.Q, c.R, c.stride, False, c.C, epi, ws, w_al, al)
 
 
 def _dgrad_s2_merged(c, w_al, al):
@@ -114,9 +116,9 @@ def _dgrad_s2_merged(c, w_al, al):
 
 
 def backward_data(c, ws=False, w_al=True, al=True):
-    """launch_dgrad; `al`: dx (and the addend) on a 16-byte boundary."""
+    """plan_data (stride 1) / plan_dgrad_s2; `al`: dx, the addend and the workspace on a 16-byte boundary."""
     if c.stride == 1:
-        return igemm(c.N, c.K, c.C, c.H, c.W, c.R, 1, True, c.C, False, ws, w_al)
+        return igemm(c.N, c.K, c.C, c.H, c.W, c.R, 1, True, c.C, False, ws, w_al, al)
     if c.H & 1 or c.W & 1:
         return None
     merged = _dgrad_s2_merged(c, w_al, al)
@@ -148,7 +150,7 @@ def _nsplit(K, C, nchunks, tile):
 
 
 def backward_weight(c, shared=False):
-    """salun_conv2d_backward_weight_ex -> (route, nsplit), or (None, 0)."""
+    """plan_wgrad -> (route, partial images the reduce adds), or (None, 0)."""
     N, C, H, W, K, R, s, pad, P, Q = c.N, c.C, c.H, c.W, c.K, c.R, c.stride, c.pad, c.P, c.Q
     if R == 1 and pad == 0 and C >= 32 and H == P * s and W == Q * s and W % 4 == 0 and _chunks_1x1(N, P, Q, s):
         return f"wgrad_1x1<{s}>", _nsplit(K, C, _chunks_1x1(N, P, Q, s), 128)

@@ -150,7 +150,58 @@ def test_mirror_agrees_with_the_library_queries_on_a_sweep():
     assert n > 10000
 
 
-# every row of the route table: the variants launch_igemm, launch_dgrad, the backward-weight chain and ring_launch choose
+# ------------------------------------------------------ the mirror against the plan the library launches from
+FWD, DGRAD, WGRAD = 0, 1, 2                                       # SALUN_ROUTE_*
+SHARED, EPI, W_UNAL, OUT_UNAL = 1, 2, 4, 8                        # SALUN_WGRAD_SHARED, SALUN_ROUTE_* flags
+AMPLE = 1 << 40                                                   # a backward-weight workspace that is never too small
+
+
+def lib_route(L, direction, c, flags=0, ws_bytes=0):
+    """salun_conv2d_route -> (label or None for SALUN_EINVAL, nsplit)."""
+    import ctypes
+    buf, ns = ctypes.create_string_buffer(256), ctypes.c_int(-1)
+    rc = L.salun_conv2d_route(direction, c.N, c.C, c.H, c.W, c.K, c.R, c.stride, c.pad, c.P, c.Q, flags, ws_bytes, buf,
+                              len(buf), ctypes.byref(ns))
+    assert rc in (0, -22), (rc, c)
+    assert (rc == 0) == bool(buf.value), (rc, buf.value, c)
+    return (buf.value.decode() if rc == 0 else None), ns.value
+
+
+def assert_routes_agree(L, c, variants=True):
+    two = (False, True) if variants else (False,)
+    fwd_ws = L.salun_conv2d_data_workspace_bytes(c.N, c.K, c.P, c.Q, c.R, c.stride)
+    dg_ws = L.salun_conv2d_data_workspace_bytes(c.N, c.C, c.H, c.W, c.R, 1) if c.stride == 1 else 0
+    for epi, ws, unal in itertools.product(two, (False, True), two):
+        got, _ = lib_route(L, FWD, c, EPI * epi | W_UNAL * unal, fwd_ws if ws else 0)
+        assert got == M.forward(c, epi=epi, ws=ws and fwd_ws > 0, w_al=not unal), ("fwd", c, epi, ws, unal)
+    for ws, unal, out_unal in itertools.product((False, True), two, two):
+        got, _ = lib_route(L, DGRAD, c, W_UNAL * unal | OUT_UNAL * out_unal, dg_ws if ws else 0)
+        assert got == M.backward_data(c, ws=ws and dg_ws > 0, w_al=not unal, al=not out_unal), ("dgrad", c, ws, unal, out_unal)
+    for shared in (False, True):
+        assert lib_route(L, WGRAD, c, SHARED * shared, AMPLE) == M.backward_weight(c, shared), ("wgrad", c, shared)
+
+
+def test_mirror_agrees_with_the_library_plans_on_the_cases():
+    """Every case, in every combination test_conv_exact_gpu.py calls it with: the label of the plan the library would
+    execute equals the mirror's, None exactly where the library answers SALUN_EINVAL, and the backward-weight split
+    counts are equal."""
+    L = _lib()
+    for c in R.CASES:
+        assert_routes_agree(L, c)
+
+
+def test_mirror_agrees_with_the_library_plans_on_a_sweep():
+    L = _lib()
+    n = 0
+    for N, C, K, H, W, (Rr, s) in itertools.product((1, 2, 3, 5, 24, 128), (3, 8, 64, 130), (3, 32, 64, 72, 130),
+                                                     (1, 2, 3, 4, 12, 16, 64), (1, 2, 4, 6, 8, 32, 128, 256),
+                                                     ((1, 1), (1, 2), (3, 1), (3, 2))):
+        assert_routes_agree(L, R.Case(N, C, H * s, W * s, K, Rr, s, Rr // 2), variants=False)
+        n += 1
+    assert n > 10000
+
+
+# every row of the route table: the variants plan_data, plan_dgrad_s2, plan_wgrad and ring_launch choose
 # among.  (Ring tile 4 is absent: its domain is empty, see test_ring_tile_4_has_an_empty_domain.)
 REQUIRED = [
     "igemm<3,1>/64/KT1WK2/fast/S1", "igemm<3,1>/64/KT1WK2/fast/S2", "igemm<3,1>/64/KT1WK2/fast/S8",

@@ -2,8 +2,8 @@
 
 bench.py's step is ResNet-18, batch 256 (ragged tails 148 / 52), train mode, `use_salun_convs` + `use_fused_bn`
 (BasicBlocks as single autograd nodes) + two-stream backward + `FusedMaskedSGD` with a ratio-0.5 mask.  The convolution
-dispatcher picks its tile variant from the shape alone (csrc/salun_conv.hip `launch_igemm` / `launch_dgrad_s2_merged` /
-`wgrad_nsplit`), so running the bench's own shapes here exercises exactly the instantiations the profile of the bench
+dispatcher picks its tile variant from the shape alone (csrc/salun_conv.hip `plan_data` / `plan_dgrad_s2` /
+`plan_wgrad`), so running the bench's own shapes here exercises exactly the instantiations the profile of the bench
 shows (`conv_igemm<3,1,2,4,1>`, `<3,1,4,4,1>`, `conv_dgrad_s2<...>`, `conv_wgrad`) — the N <= 32 cases of
 test_conv_gpu.py do not.
 

@@ -112,6 +112,8 @@ SIGNATURES = {
                                                                                           c_void_p]),
     "salun_conv2d_backward_weight_ex": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 11 + [ctypes.c_uint, c_void_p,
                                                                                                  c_size_t, c_void_p]),
+    "salun_conv2d_route": (c_int, [c_int] * 11 + [ctypes.c_uint, c_size_t, ctypes.c_char_p, c_size_t,
+                                   ctypes.POINTER(c_int)]),
     "salun_conv2d_bf16_supported": (c_int, [c_int] * 5),
     "salun_conv2d_bf16_pack_weights": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "salun_bf16_pack_weights_batch": (c_int, [c_void_p, c_int, c_void_p]),

@@ -20,31 +20,26 @@
 //     epilogue.
 // Backward-data, stride 2 (`conv_dgrad_s2`): all four output parities in one launch — shared dY patch, one
 //   accumulator per (parity, channel tile), exact FLOPs (no zero insertion), paired row stores; the per-parity
-//   `conv_igemm_tap` launches remain as the fallback for shapes outside its staging assumptions.
+//   `conv_dgrad_tap` launches remain as the fallback for shapes outside its staging assumptions.
 // Backward-weight (`conv_wgrad`): dW[k][c][r,s] = sum_pix dY[k][pix] * X[c][pix + (r,s)]: reduction over pixels,
 //   9 accumulators (one per tap) per wave, pixel range split over workgroups -> partials -> fixed-order reduce
 //   (deterministic, no float atomics); staging interleaved between the MFMAs (see the kernel).  `conv_wgrad_smallc`
 //   serves C*R*R <= 32 (the RGB stem) with the (c,r,s) combinations as the MFMA columns.
 // Ceilings (tools/micro/mfma_peak.hip): 155.6 TFLOP/s register operands, 144 with this file's LDS operand pattern.
 #include "salun_common.h"
+#include "salun_conv_plan.h"
 #include <mutex>
+#include <type_traits>
 #include <unordered_set>
 
-// salun_conv_ring.hip: the LDS-DMA ring form of the 3x3 / stride 1 backward-weight (SALUN_EINVAL = not its shape)
+// salun_conv_ring.hip: the LDS-DMA ring form of the 3x3 / stride 1 / pad 1 backward-weight; refuses (SALUN_EINVAL)
+// exactly where salun_ring_wgrad_fits (salun_conv_plan.h) does
 int salun_ring_wgrad_launch(const float *x, const float *dy, float *part, int N, int C, int H, int W, int K, int nsplit,
                             int nchunks, hipStream_t st);
 
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int CC = 8;  // reduction channels staged per chunk
-// conv_igemm's chunk: a 1x1 stride-1 convolution has one MFMA step per two channels, so an 8-channel chunk is four
-// steps between two barrier pairs (72 TFLOP/s on the DDPM attention / skip projections); 32 channels make it sixteen.
-constexpr int igemm_chunk(int R, int stride) { return (R == 1 && stride == 1) ? 32 : CC; }
-
-// reduction channels per chunk of the rectangular-tap kernel (conv_igemm_tap): 32 / taps, at least 8
-constexpr int tap_chunk(int taps) { return taps == 1 ? 32 : taps == 2 ? 16 : 8; }
 
 // One staged patch position of a thread: where it comes from in a channel plane and where it goes in LDS.
 struct PatchPos {
@@ -54,9 +49,65 @@ struct PatchPos {
 };
 
 // ---------------------------------------------------------------------------------------------------
+// What conv_igemm, conv_dgrad_tap and conv_dgrad_s2 share (conv_dgrad_s2: lane_pixel and acc_row only).  The helpers are loop free on purpose: each was admitted only
+// if every kernel's registers, spills, LDS and occupancy stayed what they were with the code written out
+// (profiles/conv_resource_usage_*.txt).  A helper with the unrolled loop inside it - the patch positions as an array,
+// the one-step-ahead MFMA loop - is optimised in another order than the same loop in the kernel's body and moved the
+// VGPR counts of most instantiations by 2 - 15, so those loops stay in the kernels.
+//
+// tile -> first image / first output row (tiles_per_img: row bands per image, 1 when a tile spans whole images)
+__device__ __forceinline__ void tile_origin(int tile, int NI, int TP, int tiles_per_img, int &n0, int &p0) {
+  if (NI > 1) { n0 = tile * NI; p0 = 0; }
+  else { n0 = tile / tiles_per_img; p0 = (tile - n0 * tiles_per_img) * TP; }
+}
+
+// One output pixel of a lane inside the workgroup tile (fixed for the whole kernel).
+struct LanePix {
+  int q, ni, p;  // column, image inside the tile, row inside the image's band
+  int off;       // tap (0,0) position in the patch
+};
+__device__ __forceinline__ LanePix lane_pixel(int mloc /*pixel inside the workgroup tile*/, int Q, int logQ, int TP,
+                                              int IH_t, int IW_t, int cs /*patch stride per output pixel*/) {
+  LanePix l;
+  l.q = mloc & (Q - 1);
+  const int pr = mloc >> logQ;  // row index inside the tile (over NI*TP rows)
+  l.ni = pr / TP;
+  l.p = pr - l.ni * TP;
+  l.off = (l.ni * IH_t + l.p * cs) * IW_t + l.q * cs;
+  return l;
+}
+
+// Patch element e (of PSZ per channel) as a staged position: (h0, w0) = source position of the patch's first element,
+// the source is [N][xC][xH][xW] with planeHW = xH * xW.
+__device__ __forceinline__ void patch_pos(PatchPos &p, int e, int PSZ, int IH_t, int IW_t, int n0, int N, int h0, int w0,
+                                          int xC, int xH, int xW, int planeHW) {
+  p.loff = e;
+  p.valid = 0;
+  p.goff = 0;
+  if (e < PSZ) {
+    const int ni = e / (IH_t * IW_t);
+    const int rem = e - ni * (IH_t * IW_t);
+    const int ih = rem / IW_t, iw = rem - ih * IW_t;
+    const int n = n0 + ni;
+    const int vh = h0 + ih, vw = w0 + iw;
+    const bool ok = (n < N) && vh >= 0 && vh < xH && vw >= 0 && vw < xW;
+    p.valid = ok;
+    p.goff = ok ? (n * xC * planeHW + vh * xW + vw) : 0;
+  }
+}
+
+// Epilogue: D[row = channel][col = pixel]; accumulator element v of a lane is row (v&3) + 8*(v>>2) (+ 4*hi, in kbase).
+__device__ __forceinline__ constexpr int acc_row(int v) { return (v & 3) + 8 * (v >> 2); }
+// The same row clamped into the tensor (klast = last real row relative to kbase): epilogue loads are unconditional — a
+// load behind a per-lane test becomes a branch with its own wait — so a row past the last channel re-reads the last one.
+__device__ __forceinline__ int acc_row_clamped(int v, int klast, int kbase) {
+  return max(min(acc_row(v), klast), -kbase);
+}
+
+// ---------------------------------------------------------------------------------------------------
 // forward / backward-data, stride-1 walk (the fast path: forward of any stride, backward-data of stride 1)
 //   R        filter size (1 or 3), square
-//   STRIDE   forward: convolution stride; DGRAD: upsampling factor of dY (conv stride is 1)
+//   STRIDE   forward: convolution stride; DGRAD: 1 (stride-2 backward-data has its own kernels below)
 //   KT       32-channel output tiles per wave
 //   WP x WK  wave grid inside the workgroup: WP pixel tiles x WK channel groups (WP*WK == 4)
 //   DGRAD    backward-data mode
@@ -64,8 +115,7 @@ struct PatchPos {
 //            channels, four MFMAs per four operand reads instead of two per three, and the weight slab of a chunk is
 //            staged once per 256 pixels instead of once per 128)
 // `x` is the tensor the patch is read from (forward: input; DGRAD: dY), `y` the tensor written.
-// `xC`/`xH`/`xW` are the dims of `x`, `yC`/`yH`/`yW` of `y`.  For DGRAD the virtual input is dY upsampled by
-// STRIDE and the padding is R-1-pad.
+// `xC`/`xH`/`xW` are the dims of `x`, `yC`/`yH`/`yW` of `y`.  For DGRAD the padding is R-1-pad.
 template <int R, int STRIDE, int KT, int WP, int WK, bool DGRAD, bool FAST, int PT = 1, bool SPLIT = false,
           bool EPI = false>
 // FAST: two waves per SIMD, not three (registers and spills, DESIGN_HISTORY.md round 3)
@@ -76,11 +126,12 @@ __global__ __launch_bounds__(256, FAST ? 2 : 1) void conv_igemm(const float *__r
                                                   int wK /*w dim0*/, const float *__restrict__ nbias /*[N][yC] or null*/,
                                                   const float *__restrict__ addend /*forward: [N][yC][yH][yW] or null*/,
                                                   int csplit /*reduction channels per blockIdx.z (0: no split)*/) {
+  static_assert(!DGRAD || STRIDE == 1, "backward-data of a stride-2 convolution: conv_dgrad_s2 / conv_dgrad_tap");
   constexpr int RS = R * R;
   constexpr int KB = WK * KT * 32;     // output channels per workgroup tile
   constexpr int CC = igemm_chunk(R, STRIDE);  // (shadows the file-wide 8)
   constexpr int WROW = CC * RS + 1;    // LDS weight row (odd => conflict-free across 32 rows)
-  constexpr int CONV_S = DGRAD ? 1 : STRIDE;
+  constexpr int CONV_S = STRIDE;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int PSZ = NI * IH_t * IW_t;
   const int ch_stride = PSZ | 1;
@@ -91,57 +142,23 @@ __global__ __launch_bounds__(256, FAST ? 2 : 1) void conv_igemm(const float *__r
   const int lo = lane & 31, hi = lane >> 5;
   const int wp = wave % WP, wk = wave / WP;
   const int Q = yW, P = yH;
-  const int tiles_per_img = (P * Q) / (TP * Q);  // row bands per image (1 when NI >= 1 image)
-  const int tile = blockIdx.x;
   const int k0 = blockIdx.y * KB;
-  // tile -> first image / first output row
   int n0, p0;
-  if (NI > 1) { n0 = tile * NI; p0 = 0; }
-  else { n0 = tile / tiles_per_img; p0 = (tile - n0 * tiles_per_img) * TP; }
+  tile_origin(blockIdx.x, NI, TP, (P * Q) / (TP * Q), n0, p0);
 
-  // ---- this lane's output pixels inside the tile (fixed for the whole kernel), one per pixel tile of the wave
-  int q_l[PT], ni_l[PT], p_l[PT], pix_off[PT];
+  // ---- this lane's output pixels inside the tile, one per pixel tile of the wave
+  LanePix lp[PT];
 #pragma unroll
-  for (int pt = 0; pt < PT; ++pt) {
-    const int mloc = (wp * PT + pt) * 32 + lo;  // 0 .. WP*PT*32-1: pixel inside the workgroup tile
-    q_l[pt] = mloc & (Q - 1);
-    const int pr = mloc >> logQ;               // row index inside the tile (over NI*TP rows)
-    ni_l[pt] = pr / TP;
-    p_l[pt] = pr - ni_l[pt] * TP;
-    pix_off[pt] = (ni_l[pt] * IH_t + p_l[pt] * CONV_S) * IW_t + q_l[pt] * CONV_S;  // tap (0,0) position in the patch
-  }
+  for (int pt = 0; pt < PT; ++pt) lp[pt] = lane_pixel((wp * PT + pt) * 32 + lo, Q, logQ, TP, IH_t, IW_t, CONV_S);
 
   // ---- the (<= 3) patch positions this thread stages for every channel of a chunk
   constexpr int MAXPOS = (R == 1 && STRIDE == 1) ? 1 : 3;  // 1x1 stride 1: the patch IS the pixel tile (<= 256)
   PatchPos pos[MAXPOS];
   const int planeHW = xH * xW;
-  // virtual (possibly upsampled) input extent
-  const int vH = DGRAD ? (xH - 1) * STRIDE + 1 : xH;
-  const int vW = DGRAD ? (xW - 1) * STRIDE + 1 : xW;
   const int vpad = DGRAD ? (R - 1 - pad) : pad;
 #pragma unroll
-  for (int j = 0; j < MAXPOS; ++j) {
-    const int e = tid + j * 256;
-    pos[j].loff = e;
-    pos[j].valid = 0;
-    pos[j].goff = 0;
-    if (e < PSZ) {
-      const int ni = e / (IH_t * IW_t);
-      const int rem = e - ni * (IH_t * IW_t);
-      const int ih = rem / IW_t, iw = rem - ih * IW_t;
-      const int n = n0 + ni;
-      const int vh = p0 * CONV_S - vpad + ih, vw = -vpad + iw;
-      bool ok = (n < N) && vh >= 0 && vh < vH && vw >= 0 && vw < vW;
-      int sh = vh, sw = vw;
-      if (DGRAD && STRIDE > 1) {
-        ok = ok && (vh % STRIDE == 0) && (vw % STRIDE == 0);
-        sh = vh / STRIDE;
-        sw = vw / STRIDE;
-      }
-      pos[j].valid = ok;
-      pos[j].goff = ok ? (n * xC * planeHW + sh * xW + sw) : 0;
-    }
-  }
+  for (int j = 0; j < MAXPOS; ++j)
+    patch_pos(pos[j], tid + j * 256, PSZ, IH_t, IW_t, n0, N, p0 * CONV_S - vpad, -vpad, xC, xH, xW, planeHW);
 
   f32x16 acc[PT][KT];
 #pragma unroll
@@ -152,7 +169,7 @@ __global__ __launch_bounds__(256, FAST ? 2 : 1) void conv_igemm(const float *__r
       for (int v = 0; v < 16; ++v) acc[pt][t][v] = 0.f;
 
   // reduction channels = channels of the tensor the patch is read from; with a reduction split (under-filled launches:
-  // launch_igemm) workgroup z covers [z * csplit, (z+1) * csplit) and writes a partial output image (no epilogue terms)
+  // plan_data) workgroup z covers [z * csplit, (z+1) * csplit) and writes a partial output image (no epilogue terms)
   // (SPLIT is a template parameter: the extra address arithmetic cost the unsplit instantiations 1.5 % of the ResNet-18
   // step when it was a run-time branch — measured on the same box, tools/_run_ab_tree.sh)
   const int cz0 = SPLIT ? (int)blockIdx.z * csplit : 0;
@@ -282,7 +299,7 @@ __global__ __launch_bounds__(256, FAST ? 2 : 1) void conv_igemm(const float *__r
     auto operands = [&](int step, float (&bv)[PT], float (&av)[KT]) {
       const int cc = 2 * (step / RS), rs = step % RS, r = rs / R, s2 = rs % R;  // compile-time after unrolling
 #pragma unroll
-      for (int pt = 0; pt < PT; ++pt) bv[pt] = pb0[pix_off[pt] + cc * ch_stride + r * IW_t + s2];
+      for (int pt = 0; pt < PT; ++pt) bv[pt] = pb0[lp[pt].off + cc * ch_stride + r * IW_t + s2];
 #pragma unroll
       for (int t = 0; t < KT; ++t) av[t] = wb0[t * 32 * WROW + cc * RS + rs];
     };
@@ -307,43 +324,41 @@ __global__ __launch_bounds__(256, FAST ? 2 : 1) void conv_igemm(const float *__r
     }
   }
 
-  // ---- epilogue: D[row = channel][col = pixel]; row = (v&3) + 8*(v>>2) + 4*hi
+  // ---- epilogue (acc_row: which channel an accumulator element is)
   // The epilogue terms of a 32-channel tile are ALL read before its first store (round 5).  Written element by element
   // (`o += bias[k]; o += addend[oi]; y[oi] = o`) every load sat behind the previous element's store — y may alias the
   // addend, so the compiler keeps the order — and waited for alone: up to 3 x 64 serial trips to memory per lane at
   // the end of the two busiest kernels of the DDPM step.
 #pragma unroll
   for (int pt = 0; pt < PT; ++pt) {
-    const int n_out = n0 + ni_l[pt], p_out = p0 + p_l[pt];
+    const int n_out = n0 + lp[pt].ni, p_out = p0 + lp[pt].p;
     if (n_out < N) {
 #pragma unroll
       for (int t = 0; t < KT; ++t) {
         const int kbase = k0 + (wk * KT + t) * 32 + 4 * hi;
-        const size_t obase = (((size_t)n_out * yC + kbase) * P + p_out) * Q + q_l[pt];
+        const size_t obase = (((size_t)n_out * yC + kbase) * P + p_out) * Q + lp[pt].q;
         const size_t kstride = (size_t)P * Q;
-        // loads are unconditional (a row past the last channel re-reads the last one): a load behind a per-lane test
-        // becomes a branch with its own wait
-        float bv[16], nv[16], av[16];
+        float bv[16], nv[16], av[16];  // loads are unconditional (acc_row_clamped)
         const int klast = yC - 1 - kbase;  // < 0: the whole tile is past the last channel (nothing is stored)
         if (bias) {
 #pragma unroll
           for (int v = 0; v < 16; ++v) {
-            const int kr = max(min((v & 3) + 8 * (v >> 2), klast), -kbase);
+            const int kr = acc_row_clamped(v, klast, kbase);
             bv[v] = DGRAD ? bias[obase + (long long)kr * (long long)kstride] : bias[kbase + kr];  // backward-data: `bias` is a full-size addend (may alias y)
           }
         }
         if (EPI && nbias) {
 #pragma unroll
-          for (int v = 0; v < 16; ++v) nv[v] = nbias[(size_t)n_out * yC + kbase + max(min((v & 3) + 8 * (v >> 2), klast), -kbase)];
+          for (int v = 0; v < 16; ++v) nv[v] = nbias[(size_t)n_out * yC + kbase + acc_row_clamped(v, klast, kbase)];
         }
         if (EPI && addend) {
 #pragma unroll
           for (int v = 0; v < 16; ++v)
-            av[v] = addend[obase + (long long)max(min((v & 3) + 8 * (v >> 2), klast), -kbase) * (long long)kstride];
+            av[v] = addend[obase + (long long)acc_row_clamped(v, klast, kbase) * (long long)kstride];
         }
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
-          const int kr = (v & 3) + 8 * (v >> 2);
+          const int kr = acc_row(v);
           if (kbase + kr < yC) {
             float o = acc[pt][t][v];
             if (bias) o += bv[v];
@@ -364,38 +379,36 @@ __global__ __launch_bounds__(256, FAST ? 2 : 1) void conv_igemm(const float *__r
 }
 
 // ---------------------------------------------------------------------------------------------------
-// tap-mapped variant (used for the parity classes of stride-2 backward-data)
-//   RH x RW  taps staged per channel (forward: the full R x R filter; backward-data with stride 2: the 1..2 x 1..2
-//            taps that reach one output parity class)
-//   STRIDE   forward convolution stride (backward-data always walks its source with stride 1)
+// backward-data of a stride-2 convolution over ONE output-parity class (the fallback of conv_dgrad_s2 below)
+//   RH x RW  the 1..2 x 1..2 taps that reach the class
 //   KT       32-channel output tiles per wave
 //   WP x WK  wave grid inside the workgroup: WP pixel tiles x WK channel groups (WP*WK == 4)
-//   DGRAD    backward-data mode: source = dY, weight slab transposed, taps taken as r_i = rtop - ts*i
+//   MAXPOS   patch positions a thread stages per channel (1: patch <= 256 floats, else 3)
 // Backward-data of a stride-2 convolution is decomposed by output parity (ph, pw): dx[2a+ph][2b+pw] only receives
 // taps r = (ph + pad) mod 2 (+2), so each class is a small dense stride-1 convolution over dY written to a
-// strided sub-grid of dx — same FLOPs as the forward pass, no zero-insertion.
-struct IgemmArgs {
-  const float *x;     // tensor the patch is read from (forward: input; DGRAD: dY)
+// strided sub-grid of dx — same FLOPs as the forward pass, no zero-insertion.  Source = dY, weight slab transposed,
+// taps taken as r_i = rtop - ts*i.
+struct TapArgs {
+  const float *x;     // tensor the patch is read from (dY)
   const float *w;     // OIHW weights [wK][wC][Rfull][Rfull]
-  const float *bias;  // optional, per output channel
-  float *y;           // tensor written (forward: output; DGRAD: dX)
+  const float *bias;  // optional full-size addend (may alias y)
+  float *y;           // tensor written (dX)
   int N, xC, xH, xW, yC, yH, yW;
   int subH, subW;          // output sub-grid walked by the tiles (yH/os, yW/os)
   int os, ph, pw;          // output position = sub * os + (ph, pw)
-  int vpad_h, vpad_w;      // patch origin: source row = p0*conv_stride - vpad_h + ih
+  int vpad_h, vpad_w;      // patch origin: source row = p0 - vpad_h + ih
   int NI, TP, IH_t, IW_t, logQ;
   int wC, wK, Rfull;
-  int rtop_h, rtop_w, ts;  // DGRAD tap mapping
+  int rtop_h, rtop_w, ts;  // tap mapping
 };
 
-template <int RH, int RW, int STRIDE, int KT, int WP, int WK, bool DGRAD, int MAXPOS>
-__global__ __launch_bounds__(256) void conv_igemm_tap(const IgemmArgs g) {
+template <int RH, int RW, int KT, int WP, int WK, int MAXPOS>
+__global__ __launch_bounds__(256) void conv_dgrad_tap(const TapArgs g) {
   constexpr int RS = RH * RW;
   constexpr int CC = tap_chunk(RS);    // reduction channels per chunk: 32 / 16 / 8 for 1 / 2 / 4 taps, so every chunk
                                        // carries 16 k-steps between its barriers whatever the parity class
   constexpr int KB = WK * KT * 32;     // output channels per workgroup tile
   constexpr int WROW = CC * RS + 1;    // LDS weight row (odd => conflict-free across 32 rows)
-  constexpr int CONV_S = DGRAD ? 1 : STRIDE;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int NI = g.NI, TP = g.TP, IH_t = g.IH_t, IW_t = g.IW_t;
   const int PSZ = NI * IH_t * IW_t;
@@ -409,40 +422,19 @@ __global__ __launch_bounds__(256) void conv_igemm_tap(const IgemmArgs g) {
   const int lo = lane & 31, hi = lane >> 5;
   const int wp = wave % WP, wk = wave / WP;
   const int Q = g.subW, P = g.subH;
-  const int tiles_per_img = P / TP;  // row bands per image (1 when a tile spans whole images)
-  const int tile = blockIdx.x;
   const int k0 = blockIdx.y * KB;
   int n0, p0;
-  if (NI > 1) { n0 = tile * NI; p0 = 0; }
-  else { n0 = tile / tiles_per_img; p0 = (tile - n0 * tiles_per_img) * TP; }
+  tile_origin(blockIdx.x, NI, TP, P / TP, n0, p0);
 
-  // ---- this lane's output pixel inside the tile (fixed for the whole kernel)
-  const int mloc = wp * 32 + lo;
-  const int q_l = mloc & (Q - 1);
-  const int pr = mloc >> g.logQ;               // row index inside the tile (over NI*TP rows)
-  const int ni_l = pr / TP, p_l = pr - ni_l * TP;
-  const int pix_off = (ni_l * IH_t + p_l * CONV_S) * IW_t + q_l * CONV_S;  // tap (0,0) position in the patch
+  // ---- this lane's output pixel inside the tile
+  const LanePix lp = lane_pixel(wp * 32 + lo, Q, g.logQ, TP, IH_t, IW_t, 1);
 
   // ---- the (<= MAXPOS) patch positions this thread stages for every channel of a chunk
   PatchPos pos[MAXPOS];
   const int xC = g.xC, planeHW = g.xH * g.xW;
 #pragma unroll
-  for (int j = 0; j < MAXPOS; ++j) {
-    const int e = tid + j * 256;
-    pos[j].loff = e;
-    pos[j].valid = 0;
-    pos[j].goff = 0;
-    if (e < PSZ) {
-      const int ni = e / (IH_t * IW_t);
-      const int rem = e - ni * (IH_t * IW_t);
-      const int ih = rem / IW_t, iw = rem - ih * IW_t;
-      const int n = n0 + ni;
-      const int vh = p0 * CONV_S - g.vpad_h + ih, vw = -g.vpad_w + iw;
-      const bool ok = (n < g.N) && vh >= 0 && vh < g.xH && vw >= 0 && vw < g.xW;
-      pos[j].valid = ok;
-      pos[j].goff = ok ? (n * xC * planeHW + vh * g.xW + vw) : 0;
-    }
-  }
+  for (int j = 0; j < MAXPOS; ++j)
+    patch_pos(pos[j], tid + j * 256, PSZ, IH_t, IW_t, n0, g.N, p0 - g.vpad_h, -g.vpad_w, xC, g.xH, g.xW, planeHW);
 
   f32x16 acc[KT];
 #pragma unroll
@@ -471,22 +463,12 @@ __global__ __launch_bounds__(256) void conv_igemm_tap(const IgemmArgs g) {
 #pragma unroll
     for (int i = 0; i < WN; ++i) {
       const int e = tid + i * 256;
-      bool ok;
-      int off;
-      if (!DGRAD) {
-        // forward: rows = output channel k; global w[k][c0..c0+CC][rs] is one contiguous run per k
-        const int kk = e / (CC * RS), j = e - kk * (CC * RS);
-        const int c = j / RS;
-        ok = (k0 + kk) < wK && (c0 + c) < wC;
-        off = (k0 + kk) * wC * RS + c0 * RS + j;
-      } else {
-        // backward-data: rows = forward input channel (output of this pass), reduction over forward k
-        const int kk = e / (KB * RS), rem = e - kk * (KB * RS);
-        const int cl = rem / RS, t = rem - cl * RS;
-        const int ti = t / RW, tj = t - ti * RW;
-        ok = (c0 + kk) < wK && (k0 + cl) < wC;
-        off = ((c0 + kk) * wC + (k0 + cl)) * RF2 + (g.rtop_h - g.ts * ti) * g.Rfull + (g.rtop_w - g.ts * tj);
-      }
+      // rows = forward input channel (output of this pass), reduction over forward k
+      const int kk = e / (KB * RS), rem = e - kk * (KB * RS);
+      const int cl = rem / RS, t = rem - cl * RS;
+      const int ti = t / RW, tj = t - ti * RW;
+      const bool ok = (c0 + kk) < wK && (k0 + cl) < wC;
+      const int off = ((c0 + kk) * wC + (k0 + cl)) * RF2 + (g.rtop_h - g.ts * ti) * g.Rfull + (g.rtop_w - g.ts * tj);
       float v = 0.f;
       if (ok) v = w[off];
       wreg[i] = v;
@@ -502,14 +484,9 @@ __global__ __launch_bounds__(256) void conv_igemm_tap(const IgemmArgs g) {
 #pragma unroll
     for (int i = 0; i < WN; ++i) {
       const int e = tid + i * 256;
-      if (!DGRAD) {
-        const int kk = e / (CC * RS), j = e - kk * (CC * RS);
-        wl[kk * WROW + j] = wreg[i];
-      } else {
-        const int kk = e / (KB * RS), rem = e - kk * (KB * RS);
-        const int cl = rem / RS, t = rem - cl * RS;
-        wl[cl * WROW + kk * RS + t] = wreg[i];
-      }
+      const int kk = e / (KB * RS), rem = e - kk * (KB * RS);
+      const int cl = rem / RS, t = rem - cl * RS;
+      wl[cl * WROW + kk * RS + t] = wreg[i];
     }
   };
 
@@ -522,7 +499,7 @@ __global__ __launch_bounds__(256) void conv_igemm_tap(const IgemmArgs g) {
     // ---- MFMA over the chunk: 2 reduction channels per instruction (lanes 0-31: cc, lanes 32-63: cc+1); the
     // (1 + KT) LDS operands of k-step i+1 are read while the KT MFMAs of k-step i run (as in conv_igemm)
     constexpr int NSTEP = (CC / 2) * RS;
-    const float *pb0 = patch + hi * ch_stride + pix_off;
+    const float *pb0 = patch + hi * ch_stride + lp.off;
     const float *wb0 = wl + (wk * KT * 32 + lo) * WROW + hi * RS;
     auto operands = [&](int step, float &bv, float (&av)[KT]) {
       const int cc = 2 * (step / RS), rs = step % RS, r = rs / RW, s2 = rs % RW;  // compile-time after unrolling
@@ -545,9 +522,9 @@ __global__ __launch_bounds__(256) void conv_igemm_tap(const IgemmArgs g) {
     }
   }
 
-  // ---- epilogue: D[row = channel][col = pixel]; row = (v&3) + 8*(v>>2) + 4*hi
-  const int n_out = n0 + ni_l;
-  const int h_out = (p0 + p_l) * g.os + g.ph, w_out = q_l * g.os + g.pw;
+  // ---- epilogue (acc_row: which channel an accumulator element is)
+  const int n_out = n0 + lp.ni;
+  const int h_out = (p0 + lp.p) * g.os + g.ph, w_out = lp.q * g.os + g.pw;
   if (n_out < g.N) {
 #pragma unroll
     for (int t = 0; t < KT; ++t) {
@@ -558,14 +535,12 @@ __global__ __launch_bounds__(256) void conv_igemm_tap(const IgemmArgs g) {
       const int klast = g.yC - 1 - kbase;
       if (g.bias) {
 #pragma unroll
-        for (int v = 0; v < 16; ++v) {
-          const int kr = max(min((v & 3) + 8 * (v >> 2), klast), -kbase);
-          bv[v] = DGRAD ? g.bias[obase + (long long)kr * (long long)kstride] : g.bias[kbase + kr];
-        }
+        for (int v = 0; v < 16; ++v)
+          bv[v] = g.bias[obase + (long long)acc_row_clamped(v, klast, kbase) * (long long)kstride];
       }
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
-        const int kr = (v & 3) + 8 * (v >> 2);
+        const int kr = acc_row(v);
         if (kbase + kr < g.yC) {
           float o = acc[t][v];
           if (g.bias) o += bv[v];
@@ -584,7 +559,7 @@ __global__ __launch_bounds__(256) void conv_igemm_tap(const IgemmArgs g) {
 // per parity class and channel tile).  The dY patch (tile rows + one halo row/column) and the full R*R weight slab of
 // a reduction chunk are staged once and serve all classes — same MFMA count as the forward pass, no zero
 // insertion, one launch instead of four, and the epilogue writes (2b, 2b+1) pairs: full coalesced rows of dX.
-// (The per-class conv_igemm_tap path stays as the fallback for shapes outside this kernel's staging assumptions.)
+// (The per-class conv_dgrad_tap path stays as the fallback for shapes outside this kernel's staging assumptions.)
 template <int R, int PAD, int KT, int WP, int WK>
 __global__ __launch_bounds__(256, 2) void conv_dgrad_s2(const float *__restrict__ dy, const float *__restrict__ w,
                                                      const float *__restrict__ addend, float *__restrict__ dx, int N,
@@ -605,18 +580,14 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_s2(const float *__restrict_
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lo = lane & 31, hi = lane >> 5;
   const int wp = wave % WP, wk = wave / WP;
+  const int c0out = blockIdx.y * KB;  // first dX channel of this workgroup
+  // (tile_origin written out: through the helper the R = 1 instantiations take one or two more SGPRs)
   const int tiles_per_img = (NI > 1) ? 1 : P / TP;
   const int tile = blockIdx.x;
-  const int c0out = blockIdx.y * KB;  // first dX channel of this workgroup
   int n0, p0;
   if (NI > 1) { n0 = tile * NI; p0 = 0; }
   else { n0 = tile / tiles_per_img; p0 = (tile - n0 * tiles_per_img) * TP; }
-
-  const int mloc = wp * 32 + lo;
-  const int q_l = mloc & (Q - 1);
-  const int pr = mloc >> logQ;
-  const int ni_l = pr / TP, p_l = pr - ni_l * TP;
-  const int pix_off = (ni_l * IH_t + p_l) * IW_t + q_l;  // patch position of offset (DMIN, DMIN)
+  const LanePix lp = lane_pixel(wp * 32 + lo, Q, logQ, TP, IH_t, IW_t, 1);  // lp.off: patch position of offset (DMIN, DMIN)
 
   // the one patch position this thread stages per reduction channel (PSZ <= 256)
   const int planePQ = P * Q;
@@ -691,7 +662,7 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_s2(const float *__restrict_
     __syncthreads();
     if (k0 + CC < K) load_chunk(k0 + CC);
     constexpr int NSTEP = CC / 2;
-    const float *pb0 = patch + hi * ch_stride + pix_off;
+    const float *pb0 = patch + hi * ch_stride + lp.off;
     const float *wb0 = wl + (wk * KT * 32 + lo) * WROW + hi * RS;
     // operands of reduction pair `step`: the FP*FP patch values around this lane's pixel and the R*R*KT weights
     auto operands = [&](int step, float (&bv)[FP * FP], float (&av)[KT][RS]) {
@@ -737,13 +708,13 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_s2(const float *__restrict_
   }
 
   // ---- epilogue: lane = sub-pixel (a, b); rows 2a, 2a+1; each store is the (2b, 2b+1) pair
-  const int n_out = n0 + ni_l;
-  const int a_out = p0 + p_l;
+  const int n_out = n0 + lp.ni;
+  const int a_out = p0 + lp.p;
   if (n_out < N) {
 #pragma unroll
     for (int t = 0; t < KT; ++t) {
       const int cbase = c0out + (wk * KT + t) * 32 + 4 * hi;
-      const size_t obase = (((size_t)n_out * C + cbase) * H + 2 * a_out) * W + 2 * q_l;
+      const size_t obase = (((size_t)n_out * C + cbase) * H + 2 * a_out) * W + 2 * lp.q;
       const size_t cstride = (size_t)H * W;
 #pragma unroll
       for (int vb = 0; vb < 16; vb += 8) {
@@ -752,7 +723,7 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_s2(const float *__restrict_
         if (addend) {
 #pragma unroll
           for (int u = 0; u < 8; ++u) {
-            const int v = vb + u, cr = max(min((v & 3) + 8 * (v >> 2), clast), -cbase);
+            const int v = vb + u, cr = acc_row_clamped(v, clast, cbase);
 #pragma unroll
             for (int ph = 0; ph < 2; ++ph)
               ad[u][ph] = *reinterpret_cast<const float2 *>(addend + obase + (long long)cr * (long long)cstride + ph * W);
@@ -760,7 +731,7 @@ __global__ __launch_bounds__(256, 2) void conv_dgrad_s2(const float *__restrict_
         }
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
-          const int v = vb + u, cr = (v & 3) + 8 * (v >> 2);
+          const int v = vb + u, cr = acc_row(v);
           if (cbase + cr < C) {
 #pragma unroll
             for (int ph = 0; ph < 2; ++ph) {
@@ -1607,12 +1578,8 @@ inline void launch_wgrad_reduce(const float *part, float *dw, int64_t n, int nsp
   }
 }
 
-// ---------------------------------------------------------------------------------------------------
-struct TileGeom {
-  int NI, TP, IH_t, IW_t, logQ;
-  int ntiles;
-  bool ok;
-};
+// ===================================================================================== host side
+// A call is planned by a pure function of its shape (salun_conv_plan.h), then launched from the plan here.
 
 // dynamic LDS above the default limit needs a per-kernel opt-in; the attribute call is a slow driver round trip,
 // so it is made once per kernel (process-wide table, the only mutable global state of the library).
@@ -1628,34 +1595,19 @@ inline void allow_lds(F fn, size_t bytes) {
   if (bytes > 48 * 1024) allow_lds_once(reinterpret_cast<const void *>(fn));
 }
 
-inline int ilog2(int v) {
-  int l = 0;
-  while ((1 << l) < v) ++l;
-  return l;
-}
-
-// pixel tiling of an output of N x P x Q into tiles of `pixt` pixels; conv stride cs, filter R
-inline TileGeom make_geom(int N, int P, int Q, int pixt, int cs, int R) {
-  TileGeom g{};
-  g.ok = false;
-  if (Q <= 0 || (Q & (Q - 1)) != 0 || Q > pixt) return g;  // Q power of two, at most one tile wide
-  g.logQ = ilog2(Q);
-  const int PQ = P * Q;
-  if (PQ >= pixt) {
-    if (PQ % pixt != 0) return g;
-    g.NI = 1;
-    g.TP = pixt / Q;
-    g.ntiles = N * (PQ / pixt);
+// f(KT, WP, WK) with the tile's wave grid as compile-time constants: the five shapes pick_tile / pick_tile_s2 produce
+template <int V>
+using ic = std::integral_constant<int, V>;
+template <typename F>
+inline void with_tile(const Tile &t, F &&f) {
+  if (t.WP == 4) {
+    if (t.KT == 4) f(ic<4>{}, ic<4>{}, ic<1>{});
+    else if (t.KT == 2) f(ic<2>{}, ic<4>{}, ic<1>{});
+    else f(ic<1>{}, ic<4>{}, ic<1>{});
   } else {
-    if (pixt % PQ != 0) return g;
-    g.NI = pixt / PQ;
-    g.TP = P;
-    g.ntiles = (N + g.NI - 1) / g.NI;
+    if (t.KT == 2) f(ic<2>{}, ic<2>{}, ic<2>{});
+    else f(ic<1>{}, ic<2>{}, ic<2>{});
   }
-  g.IH_t = (g.TP - 1) * cs + R;
-  g.IW_t = (Q - 1) * cs + R;
-  g.ok = (g.NI * g.IH_t * g.IW_t) <= 3 * 256;
-  return g;
 }
 
 // Second half of a reduction-split launch: y = sum_z part[z] (fixed order) + the epilogue terms the split workgroups
@@ -1680,248 +1632,96 @@ __global__ __launch_bounds__(256) void conv_split_finish(const float *__restrict
   *reinterpret_cast<float4 *>(y + e) = acc;
 }
 
-// Reduction split for under-filled launches (the 4x4 level of the DDPM U-Net at batch 128 is 128 workgroups of
-// 64 pixels x 64 channels: half the CUs idle, the rest with one workgroup and nothing to hide its staging behind):
-// S workgroups per output tile, each over C/S reduction channels, partial images in the caller's workspace.
-inline int igemm_split(int wgs, int xC, int chunk, size_t out_elems, int HW, const void *ws, size_t ws_bytes) {
-  if (!ws || wgs > 256 || HW % 4 != 0 || out_elems % 4 != 0) return 1;
-  int S = 512 / (wgs < 1 ? 1 : wgs);
-  if (S > 8) S = 8;
-  while (S > 1 && (xC % (S * chunk) != 0 || xC / S < 4 * chunk)) --S;  // equal shares, >= 4 chunks each
-  while (S > 1 && (size_t)S * out_elems * sizeof(float) > ws_bytes) --S;
-  return S < 1 ? 1 : S;
+struct DataArgs {
+  const float *x, *w, *bias /*DGRAD: the full-size addend*/, *nbias, *addend;
+  float *y, *part;
+  int N, xC, xH, xW, yC, yH, yW, pad, wC, wK;
+};
+
+template <int R, int STRIDE, int KT, int WP, int WK, bool DGRAD, bool FAST, int PT, bool SPLIT, bool EPI>
+void launch_one_igemm(const DataPlan &p, const DataArgs &a, hipStream_t st) {
+  const TileGeom &g = p.t.g;
+  const dim3 grid(g.ntiles, p.wgs / g.ntiles, SPLIT ? p.S : 1);
+  allow_lds(conv_igemm<R, STRIDE, KT, WP, WK, DGRAD, FAST, PT, SPLIT, EPI>, p.lds_bytes);
+  // a reduction share writes a partial image and leaves every epilogue term to conv_split_finish
+  hipLaunchKernelGGL((conv_igemm<R, STRIDE, KT, WP, WK, DGRAD, FAST, PT, SPLIT, EPI>), grid, dim3(256), p.lds_bytes, st,
+                     a.x, a.w, SPLIT ? nullptr : a.bias, SPLIT ? a.part : a.y, a.N, a.xC, a.xH, a.xW, a.yC, a.yH, a.yW,
+                     a.pad, g.NI, g.TP, g.IH_t, g.IW_t, g.logQ, a.wC, a.wK, EPI ? a.nbias : nullptr,
+                     EPI ? a.addend : nullptr, SPLIT ? a.xC / p.S : 0);
 }
 
 template <int R, int STRIDE, bool DGRAD>
-int launch_igemm(const float *x, const float *w, const float *bias, float *y, int N, int xC, int xH, int xW, int yC,
-                 int yH, int yW, int pad, int wC, int wK, hipStream_t st, const float *nbias = nullptr,
-                 const float *addend = nullptr, void *ws = nullptr, size_t ws_bytes = 0) {
-  // tile shape: prefer 128 pixels x up to 128 channels; shrink when that leaves the chip under-filled
-  const int cs = DGRAD ? 1 : STRIDE;
-  int pixt = 128;
-  TileGeom g = make_geom(N, yH, yW, pixt, cs, R);
-  const int kblocks128 = (yC + 127) / 128;
-  if (!g.ok || g.ntiles * kblocks128 < 384) {
-    TileGeom g64 = make_geom(N, yH, yW, 64, cs, R);
-    if (g64.ok) { g = g64; pixt = 64; }
-  }
-  if (!g.ok) return SALUN_EINVAL;
-  const int PSZ = g.NI * g.IH_t * g.IW_t;
-  const int ch_stride = PSZ | 1;
-  constexpr int RS = R * R;
-  constexpr int CC = igemm_chunk(R, STRIDE);  // the kernel's chunk (shadows the file-wide 8)
-  const size_t out_elems = (size_t)N * yC * yH * yW;
-  float *part = static_cast<float *>(ws);
-  const bool epi = !DGRAD && (nbias != nullptr || addend != nullptr);
-  const bool split_al16 = salun_aligned16(y) && salun_aligned16(ws) && (!addend || salun_aligned16(addend)) &&
-                          (!(DGRAD && bias) || salun_aligned16(bias));  // DGRAD: `bias` carries the full-size addend
-#define SALUN_IGEMM(KT_, WP_, WK_, SPL_)                                                                        \
-  {                                                                                                             \
-    constexpr int KB = WK_ * KT_ * 32;                                                                          \
-    const size_t ldsb = sizeof(float) * ((size_t)CC * ch_stride + (size_t)KB * (CC * RS + 1));                  \
-    dim3 grid(g.ntiles, (yC + KB - 1) / KB);                                                                    \
-    /* FAST staging: full reduction chunks, channel tile inside the tensor, float4-aligned weight runs */      \
-    const bool fast = (xC % CC == 0) && (!DGRAD || yC % KB == 0) && salun_aligned16(w) &&                       \
-                      ((wC * RS) % 4 == 0) && !(DGRAD && STRIDE > 1);                                           \
-    if (epi && (!fast || DGRAD || STRIDE != 1)) return SALUN_EINVAL; /* epilogue terms: stride-1 forward, FAST */ \
-    if (fast) {                                                                                                 \
-      int S = 1;                                                                                                \
-      /* the finishing kernel reads / writes y, the addends and the partials as float4: 16-byte bases or no split */ \
-      if constexpr (SPL_)                                                                                       \
-        if (split_al16) S = igemm_split((int)(grid.x * grid.y), xC, CC, out_elems, yH * yW, ws, ws_bytes);      \
-      if (S > 1) {                                                                                              \
-        if constexpr (SPL_) {                                                                                   \
-          grid.z = S;                                                                                           \
-          allow_lds(conv_igemm<R, STRIDE, KT_, WP_, WK_, DGRAD, true, 1, true>, ldsb);                          \
-          hipLaunchKernelGGL((conv_igemm<R, STRIDE, KT_, WP_, WK_, DGRAD, true, 1, true>), grid, dim3(256), ldsb, \
-                             st, x, w, nullptr, part, N, xC, xH, xW, yC, yH, yW, pad, g.NI, g.TP, g.IH_t,       \
-                             g.IW_t, g.logQ, wC, wK, nullptr, nullptr, xC / S);                                 \
-          SALUN_LAUNCH_CHECK();                                                                                 \
-          hipLaunchKernelGGL(conv_split_finish, dim3((unsigned)((out_elems / 4 + 255) / 256)), dim3(256), 0,    \
-                             st, part, S, out_elems, DGRAD ? nullptr : bias, nbias, addend,                     \
-                             DGRAD ? bias : nullptr, y, yC, yH * yW);                                           \
-        }                                                                                                       \
-      } else if (epi) {                                                                                         \
-        if constexpr (!DGRAD && STRIDE == 1) {                                                                  \
-          allow_lds(conv_igemm<R, STRIDE, KT_, WP_, WK_, DGRAD, true, 1, false, true>, ldsb);                   \
-          hipLaunchKernelGGL((conv_igemm<R, STRIDE, KT_, WP_, WK_, DGRAD, true, 1, false, true>), grid,         \
-                             dim3(256), ldsb, st, x, w, bias, y, N, xC, xH, xW, yC, yH, yW, pad, g.NI, g.TP,    \
-                             g.IH_t, g.IW_t, g.logQ, wC, wK, nbias, addend, 0);                                 \
-        }                                                                                                       \
-      } else {                                                                                                  \
-        allow_lds(conv_igemm<R, STRIDE, KT_, WP_, WK_, DGRAD, true>, ldsb);                                     \
-        hipLaunchKernelGGL((conv_igemm<R, STRIDE, KT_, WP_, WK_, DGRAD, true>), grid, dim3(256), ldsb, st, x, w, \
-                           bias, y, N, xC, xH, xW, yC, yH, yW, pad, g.NI, g.TP, g.IH_t, g.IW_t, g.logQ, wC, wK, \
-                           nullptr, nullptr, 0);                                                                \
-      }                                                                                                         \
-    } else {                                                                                                    \
-      allow_lds(conv_igemm<R, STRIDE, KT_, WP_, WK_, DGRAD, false>, ldsb);                                      \
-      hipLaunchKernelGGL((conv_igemm<R, STRIDE, KT_, WP_, WK_, DGRAD, false>), grid, dim3(256), ldsb, st, x, w, \
-                         bias, y, N, xC, xH, xW, yC, yH, yW, pad, g.NI, g.TP, g.IH_t, g.IW_t, g.logQ, wC, wK,   \
-                         nullptr, nullptr, 0);                                                                  \
-    }                                                                                                           \
-  }
-  if (pixt == 128) {
-    if (yC > 64) SALUN_IGEMM(4, 4, 1, false)
-    else if (yC > 32) {
-      // 64 output channels: a wave takes 64 pixels x 64 channels (PT = 2) when 256-pixel tiles still fill the chip
-      // and the stride-1 fast path applies
-      TileGeom g256 = make_geom(N, yH, yW, 256, cs, R);
-      const int ps256 = g256.ok ? g256.NI * g256.IH_t * g256.IW_t : 0;
-      const bool fast2 = (xC % CC == 0) && (!DGRAD || yC % 64 == 0) && salun_aligned16(w) && ((wC * RS) % 4 == 0) &&
-                         !(DGRAD && STRIDE > 1);
-      if (g256.ok && fast2 && g256.ntiles >= 512 && ps256 <= 768 && !epi) {
-        const int chs = ps256 | 1;
-        const size_t ldsb2 = sizeof(float) * ((size_t)CC * chs + (size_t)64 * (CC * RS + 1));
-        dim3 grid2(g256.ntiles, (yC + 63) / 64);
-        allow_lds(conv_igemm<R, STRIDE, 2, 4, 1, DGRAD, true, 2>, ldsb2);
-        hipLaunchKernelGGL((conv_igemm<R, STRIDE, 2, 4, 1, DGRAD, true, 2>), grid2, dim3(256), ldsb2, st, x, w, bias, y,
-                           N, xC, xH, xW, yC, yH, yW, pad, g256.NI, g256.TP, g256.IH_t, g256.IW_t, g256.logQ, wC, wK, nullptr,
-                           nullptr, 0);
-      } else SALUN_IGEMM(2, 4, 1, false)
-    }
-    else SALUN_IGEMM(1, 4, 1, false)
+int launch_data(const DataPlan &p, const DataArgs &a, hipStream_t st) {
+  if (p.t.PT == 2) {
+    launch_one_igemm<R, STRIDE, 2, 4, 1, DGRAD, true, 2, false, false>(p, a, st);
   } else {
-    // small pixel space (deep layers): 64 x 128 tiles only if that still yields enough workgroups
-    if (yC > 64 && g.ntiles * kblocks128 >= 384) SALUN_IGEMM(2, 2, 2, false)
-    else SALUN_IGEMM(1, 2, 2, true)  // the only tiling an under-filled launch ends up with
+    with_tile(p.t, [&](auto kt, auto wp, auto wk) {
+      constexpr int KT = decltype(kt)::value, WP = decltype(wp)::value, WK = decltype(wk)::value;
+      constexpr bool CAN_SPLIT = (WP == 2 && KT == 1), CAN_EPI = (!DGRAD && STRIDE == 1);  // as plan_data grants them
+      if (!p.fast) {
+        launch_one_igemm<R, STRIDE, KT, WP, WK, DGRAD, false, 1, false, false>(p, a, st);
+      } else if (p.S > 1) {
+        if constexpr (CAN_SPLIT) launch_one_igemm<R, STRIDE, KT, WP, WK, DGRAD, true, 1, true, false>(p, a, st);
+      } else if (p.epi) {
+        if constexpr (CAN_EPI) launch_one_igemm<R, STRIDE, KT, WP, WK, DGRAD, true, 1, false, true>(p, a, st);
+      } else {
+        launch_one_igemm<R, STRIDE, KT, WP, WK, DGRAD, true, 1, false, false>(p, a, st);
+      }
+    });
   }
-#undef SALUN_IGEMM
   SALUN_LAUNCH_CHECK();
+  if (p.S > 1) {
+    hipLaunchKernelGGL(conv_split_finish, dim3((unsigned)((p.out_elems / 4 + 255) / 256)), dim3(256), 0, st, a.part, p.S,
+                       p.out_elems, DGRAD ? nullptr : a.bias, a.nbias, a.addend, DGRAD ? a.bias : nullptr, a.y, a.yC,
+                       a.yH * a.yW);
+    SALUN_LAUNCH_CHECK();
+  }
   return SALUN_OK;
 }
 
-
-// rectangular-tap variant of make_geom (RH rows x RW cols of taps)
-inline TileGeom make_geom_rect(int N, int P, int Q, int pixt, int cs, int RH, int RW) {
-  TileGeom g = make_geom(N, P, Q, pixt, cs, RH);
-  if (!g.ok && g.NI == 0) return g;
-  g.IW_t = (Q - 1) * cs + RW;
-  g.ok = (g.NI > 0) && (g.NI * g.IH_t * g.IW_t) <= 3 * 256;
-  return g;
+// R, stride and direction of a planned call as template arguments
+inline int launch_data(const DataPlan &p, const DataArgs &a, hipStream_t st) {
+  if (p.dgrad) return p.R == 3 ? launch_data<3, 1, true>(p, a, st) : launch_data<1, 1, true>(p, a, st);
+  if (p.R == 3) return p.stride == 1 ? launch_data<3, 1, false>(p, a, st) : launch_data<3, 2, false>(p, a, st);
+  return p.stride == 1 ? launch_data<1, 1, false>(p, a, st) : launch_data<1, 2, false>(p, a, st);
 }
 
-template <int RH, int RW, int STRIDE, bool DGRAD>
-int launch_igemm_tap(IgemmArgs a, hipStream_t st) {
-  // tile shape: prefer 128 pixels x up to 128 channels; shrink when that leaves the chip under-filled
-  const int cs = DGRAD ? 1 : STRIDE;
-  int pixt = 128;
-  TileGeom g = make_geom_rect(a.N, a.subH, a.subW, pixt, cs, RH, RW);
-  const int kblocks128 = (a.yC + 127) / 128;
-  if (!g.ok || g.ntiles * kblocks128 < 384) {
-    TileGeom g64 = make_geom_rect(a.N, a.subH, a.subW, 64, cs, RH, RW);
-    if (g64.ok) { g = g64; pixt = 64; }
-  }
-  if (!g.ok) return SALUN_EINVAL;
-  a.NI = g.NI; a.TP = g.TP; a.IH_t = g.IH_t; a.IW_t = g.IW_t; a.logQ = g.logQ;
-  const int PSZ = g.NI * g.IH_t * g.IW_t;
-  const int ch_stride = PSZ | 1;
-  constexpr int RS = RH * RW;
-#define SALUN_IGEMM(KT_, WP_, WK_)                                                                     \
-  {                                                                                                    \
-    constexpr int KB = WK_ * KT_ * 32;                                                                 \
-    constexpr int CCT = tap_chunk(RS);                                                                 \
-    const size_t ldsb = sizeof(float) * ((size_t)CCT * ch_stride + (size_t)KB * (CCT * RS + 1));       \
-    dim3 grid(g.ntiles, (a.yC + KB - 1) / KB);                                                         \
-    if (PSZ <= 256) {                                                                                  \
-      allow_lds(conv_igemm_tap<RH, RW, STRIDE, KT_, WP_, WK_, DGRAD, 1>, ldsb);                        \
-      hipLaunchKernelGGL((conv_igemm_tap<RH, RW, STRIDE, KT_, WP_, WK_, DGRAD, 1>), grid, dim3(256), ldsb, st, a); \
-    } else {                                                                                           \
-      allow_lds(conv_igemm_tap<RH, RW, STRIDE, KT_, WP_, WK_, DGRAD, 3>, ldsb);                        \
-      hipLaunchKernelGGL((conv_igemm_tap<RH, RW, STRIDE, KT_, WP_, WK_, DGRAD, 3>), grid, dim3(256), ldsb, st, a); \
-    }                                                                                                  \
-  }
-  if (pixt == 128) {
-    if (a.yC > 64) SALUN_IGEMM(4, 4, 1)
-    else if (a.yC > 32) SALUN_IGEMM(2, 4, 1)
-    else SALUN_IGEMM(1, 4, 1)
-  } else {
-    // small pixel space (deep layers): 64 x 128 tiles only if that still yields enough workgroups
-    if (a.yC > 64 && g.ntiles * kblocks128 >= 384) SALUN_IGEMM(2, 2, 2)
-    else SALUN_IGEMM(1, 2, 2)
-  }
-#undef SALUN_IGEMM
-  SALUN_LAUNCH_CHECK();
-  return SALUN_OK;
+template <int R, int PAD, int KT, int WP, int WK>
+void launch_one_dgrad_s2(const Dgrad2Plan &p, const float *dy, const float *w, const float *addend, float *dx, int N,
+                         int C, int H, int W, int K, int P, int Q, hipStream_t st) {
+  const TileGeom &g = p.t.g;
+  allow_lds(conv_dgrad_s2<R, PAD, KT, WP, WK>, p.lds_bytes);
+  hipLaunchKernelGGL((conv_dgrad_s2<R, PAD, KT, WP, WK>), dim3(g.ntiles, C / p.t.kb()), dim3(256), p.lds_bytes, st, dy, w,
+                     addend, dx, N, K, P, Q, C, H, W, g.NI, g.TP, g.IH_t, g.IW_t, g.logQ);
 }
 
-// stride-2 backward-data, all parity classes in one launch (conv_dgrad_s2).  SALUN_EINVAL = not applicable.
-template <int R>
-int launch_dgrad_s2_merged(const float *dy, const float *w, const float *addend, float *dx, int N, int C, int H, int W,
-                           int K, int pad, int P, int Q, hipStream_t st) {
-  if (H != 2 * P || W != 2 * Q) return SALUN_EINVAL;
-  if (!((R == 3 && (pad == 0 || pad == 1)) || (R == 1 && pad == 0))) return SALUN_EINVAL;
-  constexpr int RS = R * R;
-  if (K % CC != 0 || !salun_aligned16(w) || (C * RS) % 4 != 0) return SALUN_EINVAL;
-  if (!salun_aligned16(dx) || (addend && !salun_aligned16(addend))) return SALUN_EINVAL;  // float2 row pairs
-  // tiles of sub-grid pixels; channel tile 64 or 128 (4*KT accumulators per wave: KT <= 2)
-  const int fp = (R == 1) ? 1 : 2;
-  int pixt = 128;
-  TileGeom g = make_geom(N, P, Q, pixt, 1, fp);
-  const int cb64 = (C + 63) / 64;
-  if (!g.ok || g.ntiles * cb64 < 256) {
-    TileGeom g64 = make_geom(N, P, Q, 64, 1, fp);
-    if (g64.ok) { g = g64; pixt = 64; }
-  }
-  if (!g.ok || g.NI * g.IH_t * g.IW_t > 256) return SALUN_EINVAL;
-  const int PSZ = g.NI * g.IH_t * g.IW_t;
-  const int ch_stride = PSZ | 1;
-#define SALUN_DGS2(PAD_, KT_, WP_, WK_)                                                                          \
-  {                                                                                                              \
-    constexpr int KB = WK_ * KT_ * 32;                                                                           \
-    if (C % KB != 0) return SALUN_EINVAL;                                                                        \
-    const size_t ldsb = sizeof(float) * ((size_t)CC * ch_stride + (size_t)KB * (CC * RS + 1));                   \
-    dim3 grid(g.ntiles, C / KB);                                                                                 \
-    allow_lds(conv_dgrad_s2<R, PAD_, KT_, WP_, WK_>, ldsb);                                                      \
-    hipLaunchKernelGGL((conv_dgrad_s2<R, PAD_, KT_, WP_, WK_>), grid, dim3(256), ldsb, st, dy, w, addend, dx, N, \
-                       K, P, Q, C, H, W, g.NI, g.TP, g.IH_t, g.IW_t, g.logQ);                                    \
-  }
-#define SALUN_DGS2_TILES(PAD_)                                                               \
-  if (pixt == 128) {                                                                         \
-    if (C % 64 == 0) SALUN_DGS2(PAD_, 2, 4, 1)                                               \
-    else SALUN_DGS2(PAD_, 1, 4, 1)                                                           \
-  } else {                                                                                   \
-    if (C % 128 == 0 && g.ntiles * (C / 128) >= 256) SALUN_DGS2(PAD_, 2, 2, 2)               \
-    else SALUN_DGS2(PAD_, 1, 2, 2)                                                           \
-  }
-  if (pad == 1) { SALUN_DGS2_TILES(1) } else { SALUN_DGS2_TILES(0) }
-#undef SALUN_DGS2_TILES
-#undef SALUN_DGS2
-  SALUN_LAUNCH_CHECK();
-  return SALUN_OK;
+template <int RH, int RW, int KT, int WP, int WK, int MAXPOS>
+void launch_one_dgrad_tap(const TapClass &c, const TapArgs &a, hipStream_t st) {
+  allow_lds(conv_dgrad_tap<RH, RW, KT, WP, WK, MAXPOS>, c.lds_bytes);
+  hipLaunchKernelGGL((conv_dgrad_tap<RH, RW, KT, WP, WK, MAXPOS>), dim3(c.t.g.ntiles, (a.yC + c.t.kb() - 1) / c.t.kb()),
+                     dim3(256), c.lds_bytes, st, a);
 }
 
-// backward-data: one launch for stride 1, one launch per output parity class for stride 2
-template <int R>
-int launch_dgrad(const float *dy, const float *w, const float *addend, float *dx, int N, int C, int H, int W, int K,
-                 int stride, int pad, int P, int Q, hipStream_t st, void *ws = nullptr, size_t ws_bytes = 0) {
-  IgemmArgs a{};
+inline int launch_dgrad_s2(const Dgrad2Plan &p, const float *dy, const float *w, const float *addend, float *dx, int N,
+                           int C, int H, int W, int K, int P, int Q, hipStream_t st) {
+  if (p.merged) {
+    with_tile(p.t, [&](auto kt, auto wp, auto wk) {
+      constexpr int KT = decltype(kt)::value, WP = decltype(wp)::value, WK = decltype(wk)::value;
+      if constexpr (KT <= 2) {  // pick_tile_s2
+        if (p.R == 1) launch_one_dgrad_s2<1, 0, KT, WP, WK>(p, dy, w, addend, dx, N, C, H, W, K, P, Q, st);
+        else if (p.pad == 1) launch_one_dgrad_s2<3, 1, KT, WP, WK>(p, dy, w, addend, dx, N, C, H, W, K, P, Q, st);
+        else launch_one_dgrad_s2<3, 0, KT, WP, WK>(p, dy, w, addend, dx, N, C, H, W, K, P, Q, st);
+      }
+    });
+    SALUN_LAUNCH_CHECK();
+    return SALUN_OK;
+  }
+  TapArgs a{};
   a.x = dy; a.w = w; a.bias = addend; a.y = dx;
   a.N = N; a.xC = K; a.xH = P; a.xW = Q; a.yC = C; a.yH = H; a.yW = W;
-  a.wC = C; a.wK = K; a.Rfull = R;
-  if (stride == 1) {
-    a.subH = H; a.subW = W; a.os = 1; a.ph = a.pw = 0;
-    a.rtop_h = a.rtop_w = R - 1; a.ts = 1;
-    return launch_igemm<R, 1, true>(dy, w, addend, dx, N, K, P, Q, C, H, W, pad, C, K, st, nullptr, nullptr, ws, ws_bytes);
-  }
-  if ((H & 1) || (W & 1)) return SALUN_EINVAL;
-  {
-    const int rc = launch_dgrad_s2_merged<R>(dy, w, addend, dx, N, C, H, W, K, pad, P, Q, st);
-    if (rc != SALUN_EINVAL) return rc;  // SALUN_EINVAL: outside the merged kernel's domain -> per-class path below
-  }
+  a.wC = C; a.wK = K; a.Rfull = p.R;
   a.subH = H / 2; a.subW = W / 2; a.os = 2; a.ts = 2;
-  // taps of parity class p: r = (p + pad) mod 2, +2, ... < R ; rtop = the largest
-  int ntap[2], rtop[2];
-  for (int p = 0; p < 2; ++p) {
-    const int r0 = (p + pad) & 1;
-    ntap[p] = (r0 < R) ? (R - 1 - r0) / 2 + 1 : 0;
-    rtop[p] = r0 + 2 * (ntap[p] - 1);
-  }
-  bool any_empty = false;
-  for (int ph = 0; ph < 2; ++ph)
-    for (int pw = 0; pw < 2; ++pw)
-      if (ntap[ph] == 0 || ntap[pw] == 0) any_empty = true;
-  if (any_empty) {  // positions no tap reaches: 0, or the addend itself
+  if (p.any_empty) {  // positions no tap reaches: 0, or the addend itself
     const size_t bytes = sizeof(float) * (size_t)N * C * H * W;
     if (!addend) {
       if (hipMemsetAsync(dx, 0, bytes, st) != hipSuccess) return SALUN_EIO;
@@ -1930,65 +1730,100 @@ int launch_dgrad(const float *dy, const float *w, const float *addend, float *dx
       a.bias = dx;  // the covered classes now accumulate in place
     }
   }
-  for (int ph = 0; ph < 2; ++ph)
-    for (int pw = 0; pw < 2; ++pw) {
-      if (ntap[ph] == 0 || ntap[pw] == 0) continue;
-      a.ph = ph; a.pw = pw;
-      a.rtop_h = rtop[ph]; a.rtop_w = rtop[pw];
-      a.vpad_h = -((ph + pad - rtop[ph]) / 2);  // (ph + pad - rtop) is even and <= 0
-      a.vpad_w = -((pw + pad - rtop[pw]) / 2);
-      int rc;
-      if (ntap[ph] == 1 && ntap[pw] == 1) rc = launch_igemm_tap<1, 1, 1, true>(a, st);
-      else if (ntap[ph] == 1 && ntap[pw] == 2) rc = launch_igemm_tap<1, 2, 1, true>(a, st);
-      else if (ntap[ph] == 2 && ntap[pw] == 1) rc = launch_igemm_tap<2, 1, 1, true>(a, st);
-      else if (ntap[ph] == 2 && ntap[pw] == 2) rc = launch_igemm_tap<2, 2, 1, true>(a, st);
-      else return SALUN_EINVAL;
-      if (rc != SALUN_OK) return rc;
-    }
+  for (int i = 0; i < p.ncls; ++i) {
+    const TapClass &c = p.cls[i];
+    const TileGeom &g = c.t.g;
+    a.ph = c.ph; a.pw = c.pw;
+    a.rtop_h = c.rtop_h; a.rtop_w = c.rtop_w; a.vpad_h = c.vpad_h; a.vpad_w = c.vpad_w;
+    a.NI = g.NI; a.TP = g.TP; a.IH_t = g.IH_t; a.IW_t = g.IW_t; a.logQ = g.logQ;
+    with_tile(c.t, [&](auto kt, auto wp, auto wk) {
+      constexpr int KT = decltype(kt)::value, WP = decltype(wp)::value, WK = decltype(wk)::value;
+      auto taps = [&](auto rh, auto rw) {
+        constexpr int RH = decltype(rh)::value, RW = decltype(rw)::value;
+        if (c.maxpos == 1) launch_one_dgrad_tap<RH, RW, KT, WP, WK, 1>(c, a, st);
+        else launch_one_dgrad_tap<RH, RW, KT, WP, WK, 3>(c, a, st);
+      };
+      if (c.RH == 1 && c.RW == 1) taps(ic<1>{}, ic<1>{});
+      else if (c.RH == 1) taps(ic<1>{}, ic<2>{});
+      else if (c.RW == 1) taps(ic<2>{}, ic<1>{});
+      else taps(ic<2>{}, ic<2>{});
+    });
+    SALUN_LAUNCH_CHECK();
+  }
   return SALUN_OK;
 }
 
-// 1x1 backward-weight (conv_wgrad_1x1): geometry and split count; 0 chunks = shape outside its domain
-inline int wgrad1x1_chunks(int N, int P, int Q, int stride) {
-  const int PQ = P * Q;
-  if (PQ % 4 != 0 || (stride == 2 && Q % 4 != 0)) return 0;
-  if (PQ >= 64) return (PQ % 64 == 0) ? N * (PQ / 64) : 0;
-  return (64 % PQ == 0) ? (N + 64 / PQ - 1) / (64 / PQ) : 0;
+struct WgradArgs {
+  const float *x, *dy;
+  float *part;
+  int N, C, H, W, K, P, Q, pad;
+};
+
+template <int STRIDE>
+void launch_one_wgrad_1x1(const WgradPlan &p, const WgradArgs &a, hipStream_t st) {
+  allow_lds(conv_wgrad_1x1<STRIDE>, p.lds_bytes);
+  hipLaunchKernelGGL(conv_wgrad_1x1<STRIDE>, dim3((a.K + 127) / 128, (a.C + 127) / 128, p.gz), dim3(256), p.lds_bytes, st,
+                     a.x, a.dy, a.part, a.N, a.C, a.H, a.W, a.K, a.P, a.Q, p.nchunks);
 }
-inline int wgrad1x1_nsplit(int K, int C, int nchunks) {
-  const int tiles = ((K + 127) / 128) * ((C + 127) / 128);
-  int ns = (256 + tiles - 1) / tiles;
-  if (ns > nchunks) ns = nchunks;
-  return ns < 1 ? 1 : ns;
+template <int R, int STRIDE>
+void launch_one_wgrad_smallc(const WgradPlan &p, const WgradArgs &a, hipStream_t st) {
+  const TileGeom &g = p.g;
+  hipLaunchKernelGGL((conv_wgrad_smallc<R, STRIDE>), dim3((a.K + 63) / 64, 1, p.gz), dim3(256), p.lds_bytes, st, a.x, a.dy,
+                     a.part, a.N, a.C, a.H, a.W, a.K, a.P, a.Q, a.pad, g.NI, g.TP, g.IH_t, g.IW_t, g.logQ, g.ntiles);
+}
+template <int STRIDE, int NIT>
+void launch_one_wgrad_v(const WgradPlan &p, const WgradArgs &a, hipStream_t st) {
+  const TileGeom &g = p.g;
+  allow_lds(conv_wgrad_v<STRIDE, NIT>, p.lds_bytes);
+  hipLaunchKernelGGL((conv_wgrad_v<STRIDE, NIT>), dim3((a.K + 63) / 64, (a.C + 63) / 64, p.gz), dim3(256), p.lds_bytes, st,
+                     a.x, a.dy, a.part, a.N, a.C, a.H, a.W, a.K, a.P, a.Q, g.NI, g.TP, g.IH_t, g.IW_t, g.logQ, g.ntiles);
+}
+template <int R, int STRIDE, bool FULLC>
+void launch_one_wgrad(const WgradPlan &p, const WgradArgs &a, hipStream_t st) {
+  const TileGeom &g = p.g;
+  allow_lds(conv_wgrad<R, STRIDE, FULLC>, p.lds_bytes);
+  hipLaunchKernelGGL((conv_wgrad<R, STRIDE, FULLC>), dim3((a.K + 63) / 64, (a.C + 63) / 64, p.gz), dim3(256), p.lds_bytes,
+                     st, a.x, a.dy, a.part, a.N, a.C, a.H, a.W, a.K, a.P, a.Q, a.pad, g.NI, g.TP, g.IH_t, g.IW_t, g.logQ,
+                     g.ntiles);
 }
 
-inline int wgrad_nsplit(int K, int C, int nchunks) {
-  const int tiles = ((K + 63) / 64) * ((C + 63) / 64);
-  // one workgroup per CU is resident (register budget): a single full round of 256 workgroups, each with a long
-  // run of chunks, beats more and shorter splits (prologue/epilogue and partial-sum traffic scale with nsplit)
-  // (round 5 sweep on the ResNet-18 step, profiles/r05_wgrad_sweep.txt: 128 / 192 / 256 / 384 / 512 target workgroups
-  // -> 94.4 / 107.3 / 114.7 / 103.4 / 106.1 steps/s)
-  int ns = (256 + tiles - 1) / tiles;
-  if (ns > nchunks) ns = nchunks;
-  if (ns < 1) ns = 1;
-  return ns;
+// f(R, STRIDE) as compile-time constants
+template <typename F>
+inline void with_filter(int R, int stride, F &&f) {
+  if (R == 3) { if (stride == 1) f(ic<3>{}, ic<1>{}); else f(ic<3>{}, ic<2>{}); }
+  else { if (stride == 1) f(ic<1>{}, ic<1>{}); else f(ic<1>{}, ic<2>{}); }
 }
 
-// workgroups launch_igemm would start for an output of [N, outC, outH, outW] (mirrors its tile choice); -1: outside
-// the tiling domain
-inline int igemm_wgs(int N, int outC, int outH, int outW, int cs, int R) {
-  TileGeom g = make_geom(N, outH, outW, 128, cs, R);
-  const int kblocks128 = (outC + 127) / 128;
-  int pixt = 128;
-  if (!g.ok || g.ntiles * kblocks128 < 384) {
-    TileGeom g64 = make_geom(N, outH, outW, 64, cs, R);
-    if (g64.ok) { g = g64; pixt = 64; }
+// the partial sums of a planned backward-weight call (the reduce kernel follows)
+inline int launch_wgrad(const WgradPlan &p, const WgradArgs &a, hipStream_t st) {
+  switch (p.route) {
+    case WG_1X1:
+      if (p.stride == 1) launch_one_wgrad_1x1<1>(p, a, st);
+      else launch_one_wgrad_1x1<2>(p, a, st);
+      break;
+    case WG_SMALLC:
+      with_filter(p.R, p.stride, [&](auto r, auto s) { launch_one_wgrad_smallc<decltype(r)::value, decltype(s)::value>(p, a, st); });
+      break;
+    case WG_RING:
+      return salun_ring_wgrad_launch(a.x, a.dy, a.part, a.N, a.C, a.H, a.W, a.K, p.gz, p.nchunks, st);
+    case WG_V:
+      switch (p.stride * 100 + p.nit) {
+        case 105: launch_one_wgrad_v<1, 5>(p, a, st); break;
+        case 106: launch_one_wgrad_v<1, 6>(p, a, st); break;
+        case 108: launch_one_wgrad_v<1, 8>(p, a, st); break;
+        case 209: launch_one_wgrad_v<2, 9>(p, a, st); break;
+        default: launch_one_wgrad_v<2, 10>(p, a, st); break;
+      }
+      break;
+    case WG_GENERAL:
+      with_filter(p.R, p.stride, [&](auto r, auto s) {
+        if (p.fullC) launch_one_wgrad<decltype(r)::value, decltype(s)::value, true>(p, a, st);
+        else launch_one_wgrad<decltype(r)::value, decltype(s)::value, false>(p, a, st);
+      });
+      break;
   }
-  if (!g.ok) return -1;
-  int KB;
-  if (pixt == 128) KB = outC > 64 ? 128 : outC > 32 ? 64 : 32;
-  else KB = (outC > 64 && g.ntiles * kblocks128 >= 384) ? 128 : 64;
-  return g.ntiles * ((outC + KB - 1) / KB);
+  SALUN_LAUNCH_CHECK();
+  return SALUN_OK;
 }
 
 }  // namespace
@@ -1999,8 +1834,9 @@ inline int igemm_wgs(int N, int outC, int outH, int outW, int cs, int R) {
 // is the forward stride for the forward pass and 1 for backward-data.  0 when the launch would not be split.
 SALUN_EXPORT size_t salun_conv2d_data_workspace_bytes(int N, int outC, int outH, int outW, int R, int conv_stride) {
   if (N < 1 || outC < 1 || outH < 1 || outW < 1 || (R != 1 && R != 3) || (conv_stride != 1 && conv_stride != 2)) return 0;
-  const int wgs = igemm_wgs(N, outC, outH, outW, conv_stride, R);
-  if (wgs < 0 || wgs > 256 || (outH * outW) % 4 != 0) return 0;
+  // the workgroups of the plan (whatever its reduction channels: a PT = 2 launch has >= 512 of them)
+  const DataPlan p = plan_data(N, 1, outC, outH, outW, R, conv_stride, false, 1, false, false, false, 0);
+  if (p.rc != SALUN_OK || p.wgs > 256 || (outH * outW) % 4 != 0) return 0;
   return (size_t)8 * N * outC * outH * outW * sizeof(float);
 }
 
@@ -2011,17 +1847,13 @@ SALUN_EXPORT int salun_conv2d_forward_fused(const float *x, const float *w, cons
                                             const float *addend, float *y, int N, int C, int H, int W, int K, int R,
                                             int stride, int pad, int P, int Q, void *ws, size_t ws_bytes,
                                             salun_stream_t stream) {
-  if (!x || !w || !y || N < 1 || C < 1 || K < 1 || P < 1 || Q < 1 || addend == y) return SALUN_EINVAL;
-  hipStream_t st = salun_hip_stream(stream);
-  if (R == 3 && stride == 1)
-    return launch_igemm<3, 1, false>(x, w, bias, y, N, C, H, W, K, P, Q, pad, C, K, st, nbias, addend, ws, ws_bytes);
-  if (R == 3 && stride == 2)
-    return launch_igemm<3, 2, false>(x, w, bias, y, N, C, H, W, K, P, Q, pad, C, K, st, nbias, addend, ws, ws_bytes);
-  if (R == 1 && stride == 1)
-    return launch_igemm<1, 1, false>(x, w, bias, y, N, C, H, W, K, P, Q, pad, C, K, st, nbias, addend, ws, ws_bytes);
-  if (R == 1 && stride == 2)
-    return launch_igemm<1, 2, false>(x, w, bias, y, N, C, H, W, K, P, Q, pad, C, K, st, nbias, addend, ws, ws_bytes);
-  return SALUN_EINVAL;
+  if (!x || !w || !y || addend == y) return SALUN_EINVAL;
+  const bool split_al16 = salun_aligned16(y) && salun_aligned16(ws) && (!addend || salun_aligned16(addend));
+  const DataPlan p = plan_data(N, C, K, P, Q, R, stride, false, C, nbias != nullptr || addend != nullptr,
+                               salun_aligned16(w), split_al16, ws ? ws_bytes : 0);
+  if (p.rc != SALUN_OK) return p.rc;
+  const DataArgs a{x, w, bias, nbias, addend, y, static_cast<float *>(ws), N, C, H, W, K, P, Q, pad, C, K};
+  return launch_data(p, a, salun_hip_stream(stream));
 }
 
 SALUN_EXPORT int salun_conv2d_forward(const float *x, const float *w, const float *bias, float *y, int N, int C,
@@ -2035,12 +1867,20 @@ SALUN_EXPORT int salun_conv2d_forward(const float *x, const float *w, const floa
 SALUN_EXPORT int salun_conv2d_backward_data_ws(const float *dy, const float *w, const float *addend, float *dx, int N,
                                                int C, int H, int W, int K, int R, int stride, int pad, int P, int Q,
                                                void *ws, size_t ws_bytes, salun_stream_t stream) {
-  if (!dy || !w || !dx || N < 1 || C < 1 || K < 1 || P < 1 || Q < 1) return SALUN_EINVAL;
-  if (stride != 1 && stride != 2) return SALUN_EINVAL;
+  if (!dy || !w || !dx || P < 1 || Q < 1) return SALUN_EINVAL;
   hipStream_t st = salun_hip_stream(stream);
-  if (R == 3) return launch_dgrad<3>(dy, w, addend, dx, N, C, H, W, K, stride, pad, P, Q, st, ws, ws_bytes);
-  if (R == 1) return launch_dgrad<1>(dy, w, addend, dx, N, C, H, W, K, stride, pad, P, Q, st, ws, ws_bytes);
-  return SALUN_EINVAL;
+  const bool out_al16 = salun_aligned16(dx) && (!addend || salun_aligned16(addend));
+  if (stride == 1) {  // the forward loop over dY, weight slab transposed and tap-flipped
+    const DataPlan p = plan_data(N, K, C, H, W, R, 1, true, C, false, salun_aligned16(w), out_al16 && salun_aligned16(ws),
+                                 ws ? ws_bytes : 0);
+    if (p.rc != SALUN_OK) return p.rc;
+    const DataArgs a{dy, w, addend, nullptr, nullptr, dx, static_cast<float *>(ws), N, K, P, Q, C, H, W, pad, C, K};
+    return launch_data(p, a, st);
+  }
+  if (stride != 2) return SALUN_EINVAL;
+  const Dgrad2Plan p = plan_dgrad_s2(N, C, H, W, K, R, pad, P, Q, salun_aligned16(w), out_al16);
+  if (p.rc != SALUN_OK) return p.rc;
+  return launch_dgrad_s2(p, dy, w, addend, dx, N, C, H, W, K, P, Q, st);
 }
 
 SALUN_EXPORT int salun_conv2d_backward_data_add(const float *dy, const float *w, const float *addend, float *dx, int N,
@@ -2055,18 +1895,17 @@ SALUN_EXPORT int salun_conv2d_backward_data(const float *dy, const float *w, flo
   return salun_conv2d_backward_data_add(dy, w, nullptr, dx, N, C, H, W, K, R, stride, pad, P, Q, stream);
 }
 
+// It cannot see stride or pad, so it is an upper bound over the kernels a shape may get, built from their nsplit helpers.
 SALUN_EXPORT size_t salun_conv2d_wgrad_workspace_bytes(int N, int C, int K, int R, int P, int Q) {
   // upper bound over both chunk sizes (64 pixels for stride 1, 32 for stride 2)
   TileGeom g = make_geom(N, P, Q, 32, 1, R);
   if (!g.ok) g = make_geom(N, P, Q, 64, 1, R);
   if (!g.ok) return 0;
   int ns = wgrad_nsplit(K, C, g.ntiles);
-  if (C * R * R <= 32 && C <= 4) {  // small-C kernel: up to 1024 workgroups x 2 pixel halves
-    int nss = 1024 / ((K + 63) / 64);
-    TileGeom g64 = make_geom(N, P, Q, 64, 1, R);
-    const int nt = g64.ok && g64.ntiles > g.ntiles ? g64.ntiles : g.ntiles;
-    if (nss > nt) nss = nt;
-    if (nss * 2 > ns) ns = nss * 2;
+  if (wgrad_is_smallc(C, R)) {
+    const TileGeom g64 = make_geom(N, P, Q, 64, 1, R);
+    const int nss = 2 * wgrad_smallc_nsplit(K, g64.ok && g64.ntiles > g.ntiles ? g64.ntiles : g.ntiles);
+    if (nss > ns) ns = nss;
   }
   if (R == 1) {  // conv_wgrad_1x1 splits deeper (128 x 128 tiles): size for whichever kernel the shape gets
     const int nc1 = wgrad1x1_chunks(N, P, Q, 1);
@@ -2153,122 +1992,47 @@ SALUN_EXPORT int salun_conv2d_backward_weight(const float *x, const float *dy, f
 SALUN_EXPORT int salun_conv2d_backward_weight_ex(const float *x, const float *dy, float *dw, int N, int C, int H, int W,
                                                  int K, int R, int stride, int pad, int P, int Q, int accumulate,
                                                  unsigned flags, void *ws, size_t ws_bytes, salun_stream_t stream) {
-  if (!x || !dy || !dw || !ws || N < 1 || C < 1 || K < 1 || P < 1 || Q < 1) return SALUN_EINVAL;
-  if (!((R == 3 || R == 1) && (stride == 1 || stride == 2))) return SALUN_EINVAL;
-  if (R == 1 && pad == 0 && C >= 32 && H == P * stride && W == Q * stride && W % 4 == 0 && salun_aligned16(x) &&
-      salun_aligned16(dy) && (size_t)64 * C * H * W < (1u << 30) && (size_t)64 * K * P * Q < (1u << 30)) {
-    const int nc1 = wgrad1x1_chunks(N, P, Q, stride);
-    if (nc1 > 0) {  // GEMM-shaped 1x1 kernel
-      hipStream_t st1 = salun_hip_stream(stream);
-      const int ns1 = wgrad1x1_nsplit(K, C, nc1);
-      if (ws_bytes < sizeof(float) * (size_t)ns1 * K * C) return SALUN_ENOSPC;
-      const size_t lds1 = sizeof(float) * 2 * 2 * 128 * 65;
-      dim3 grid1((K + 127) / 128, (C + 127) / 128, ns1);
-      float *part1 = static_cast<float *>(ws);
-      if (stride == 1) {
-        allow_lds(conv_wgrad_1x1<1>, lds1);
-        hipLaunchKernelGGL(conv_wgrad_1x1<1>, grid1, dim3(256), lds1, st1, x, dy, part1, N, C, H, W, K, P, Q, nc1);
-      } else {
-        allow_lds(conv_wgrad_1x1<2>, lds1);
-        hipLaunchKernelGGL(conv_wgrad_1x1<2>, grid1, dim3(256), lds1, st1, x, dy, part1, N, C, H, W, K, P, Q, nc1);
-      }
-      SALUN_LAUNCH_CHECK();
-      launch_wgrad_reduce(part1, dw, (int64_t)K * C, ns1, accumulate, K * C, 1, st1);
-      SALUN_LAUNCH_CHECK();
-      return SALUN_OK;
-    }
-  }
-  const int pixc = (stride == 1) ? 64 : 32;
-  TileGeom g = make_geom(N, P, Q, pixc, stride, R);
-  if (!g.ok || g.NI * g.IH_t * g.IW_t > 256) return SALUN_EINVAL;
+  if (!x || !dy || !dw || !ws) return SALUN_EINVAL;
+  const WgradPlan p = plan_wgrad(N, C, H, W, K, R, stride, pad, P, Q, (flags & SALUN_WGRAD_SHARED) != 0,
+                                 salun_aligned16(x) && salun_aligned16(dy), ws_bytes);
+  if (p.rc != SALUN_OK) return p.rc;
   hipStream_t st = salun_hip_stream(stream);
-  if (C * R * R <= 32 && C <= 4 && Q >= 4 && (g.TP & (g.TP - 1)) == 0) {  // RGB stem: columns = (c, r, s)
-    int ns = 1024 / ((K + 63) / 64);
-    if (ns > g.ntiles) ns = g.ntiles;
-    if (ns < 1) ns = 1;
-    const size_t need_s = sizeof(float) * (size_t)ns * 2 * K * C * R * R;
-    if (ws_bytes < need_s) return SALUN_ENOSPC;
-    const int PSZs = g.NI * g.IH_t * g.IW_t;
-    const size_t ldss = sizeof(float) * ((size_t)C * (PSZs | 1) + (size_t)64 * (pixc + 1));
-    dim3 grid_s((K + 63) / 64, 1, ns);
-    float *part_s = static_cast<float *>(ws);
-#define SALUN_WGRAD_S(R_, S_)                                                                                  \
-  hipLaunchKernelGGL((conv_wgrad_smallc<R_, S_>), grid_s, dim3(256), ldss, st, x, dy, part_s, N, C, H, W, K, P, \
-                     Q, pad, g.NI, g.TP, g.IH_t, g.IW_t, g.logQ, g.ntiles)
-    if (R == 3 && stride == 1) SALUN_WGRAD_S(3, 1);
-    else if (R == 3 && stride == 2) SALUN_WGRAD_S(3, 2);
-    else if (R == 1 && stride == 1) SALUN_WGRAD_S(1, 1);
-    else SALUN_WGRAD_S(1, 2);
-#undef SALUN_WGRAD_S
-    SALUN_LAUNCH_CHECK();
-    const int64_t nn = (int64_t)K * C * R * R;
-    launch_wgrad_reduce(part_s, dw, nn, ns * 2, accumulate, K * C, R * R, st);
-    SALUN_LAUNCH_CHECK();
-    return SALUN_OK;
-  }
-  const int ns = wgrad_nsplit(K, C, g.ntiles);
-  const size_t need = sizeof(float) * (size_t)ns * K * C * R * R;
-  if (ws_bytes < need) return SALUN_ENOSPC;
-  const int PSZ = g.NI * g.IH_t * g.IW_t;
-  if (Q < 4 || (g.TP & (g.TP - 1)) != 0) return SALUN_EINVAL;  // float4 dy staging; shift-only pixel decoding
-  const size_t ldsb = sizeof(float) * 2 * ((size_t)64 * (PSZ | 1) + (size_t)64 * (pixc + 1) + 256);  // double buffered
-  // per-lane offsets inside one chunk's image block are 32-bit
-  if ((size_t)g.NI * C * H * W >= (1u << 30) || (size_t)g.NI * K * P * Q >= (1u << 30)) return SALUN_EINVAL;
-  if (ldsb > 160 * 1024) return SALUN_EINVAL;
-  dim3 grid((K + 63) / 64, (C + 63) / 64, ns);
-  float *part = static_cast<float *>(ws);
-  // 3x3 / stride 1 / pad 1 on square images: the LDS-DMA ring kernel (salun_conv_ring.hip)
-  bool vec_done = false;
-  // ... unless the caller says the launch shares the device with another stream's kernels (SALUN_WGRAD_SHARED): beside a
-  // second matrix kernel or a BatchNorm pass on the same SIMDs the ring kernel's dense MFMA stream buys nothing and costs
-  // its neighbours more than conv_wgrad_v's does (round 6: ResNet-18 step 117.5 vs 116.1 steps/s, DDPM 9.59 vs 9.46 with
-  // backward-weight on the side stream; alone it is 12 - 18 % faster, and the single-stream step 111.8 vs 107.9)
-  if (R == 3 && stride == 1 && pad == 1 && P == H && Q == W && pixc == 64 && !(flags & SALUN_WGRAD_SHARED)) {
-    const int rc = salun_ring_wgrad_launch(x, dy, part, N, C, H, W, K, ns, g.ntiles, st);
-    if (rc == SALUN_OK) vec_done = true;
-    else if (rc != SALUN_EINVAL) return rc;
-  }
-  // vectorised staging (conv_wgrad_v) where the geometry allows it: 3x3, pad 1, full channel tiles, whole image rows
-  if (!vec_done && R == 3 && pad == 1 && C % 64 == 0 && W % 4 == 0 && Q * stride == W && P * stride == H && salun_aligned16(x) &&
-      salun_aligned16(dy) && (size_t)g.NI * C * H * W < (1u << 30)) {
-    const int F4C = g.NI * g.IH_t * (W / 4);
-    const int nit = (F4C % 4 == 0) ? F4C / 4 : 0;
-#define SALUN_WGRAD_V(S_, NIT_)                                                                                \
-  {                                                                                                            \
-    allow_lds(conv_wgrad_v<S_, NIT_>, ldsb);                                                                   \
-    hipLaunchKernelGGL((conv_wgrad_v<S_, NIT_>), grid, dim3(256), ldsb, st, x, dy, part, N, C, H, W, K, P, Q,  \
-                       g.NI, g.TP, g.IH_t, g.IW_t, g.logQ, g.ntiles);                                          \
-    vec_done = true;                                                                                           \
-  }
-    if (stride == 1) {
-      if (nit == 5) SALUN_WGRAD_V(1, 5)
-      else if (nit == 6) SALUN_WGRAD_V(1, 6)
-      else if (nit == 8) SALUN_WGRAD_V(1, 8)
-    } else {
-      if (nit == 9) SALUN_WGRAD_V(2, 9)
-      else if (nit == 10) SALUN_WGRAD_V(2, 10)
-    }
-#undef SALUN_WGRAD_V
-  }
-#define SALUN_WGRAD(R_, S_)                                                                                    \
-  if (C % 64 == 0) {                                                                                           \
-    allow_lds(conv_wgrad<R_, S_, true>, ldsb);                                                                 \
-    hipLaunchKernelGGL((conv_wgrad<R_, S_, true>), grid, dim3(256), ldsb, st, x, dy, part, N, C, H, W, K, P,   \
-                       Q, pad, g.NI, g.TP, g.IH_t, g.IW_t, g.logQ, g.ntiles);                                  \
-  } else {                                                                                                     \
-    allow_lds(conv_wgrad<R_, S_, false>, ldsb);                                                                \
-    hipLaunchKernelGGL((conv_wgrad<R_, S_, false>), grid, dim3(256), ldsb, st, x, dy, part, N, C, H, W, K, P,  \
-                       Q, pad, g.NI, g.TP, g.IH_t, g.IW_t, g.logQ, g.ntiles);                                  \
-  }
-  if (vec_done) { }
-  else if (R == 3 && stride == 1) { SALUN_WGRAD(3, 1) }
-  else if (R == 3 && stride == 2) { SALUN_WGRAD(3, 2) }
-  else if (R == 1 && stride == 1) { SALUN_WGRAD(1, 1) }
-  else { SALUN_WGRAD(1, 2) }
-#undef SALUN_WGRAD
-  SALUN_LAUNCH_CHECK();
-  const int64_t n = (int64_t)K * C * R * R;
-  launch_wgrad_reduce(part, dw, n, ns, accumulate, K * C, R * R, st);
+  const WgradArgs a{x, dy, static_cast<float *>(ws), N, C, H, W, K, P, Q, pad};
+  const int rc = launch_wgrad(p, a, st);
+  if (rc != SALUN_OK) return rc;
+  launch_wgrad_reduce(a.part, dw, (int64_t)K * C * R * R, p.nsplit, accumulate, K * C, R * R, st);
   SALUN_LAUNCH_CHECK();
   return SALUN_OK;
+}
+
+// The route label of the plan the matching entry point would execute (see include/salun.h); touches no device.
+SALUN_EXPORT int salun_conv2d_route(int direction, int N, int C, int H, int W, int K, int R, int stride, int pad, int P,
+                                    int Q, unsigned flags, size_t ws_bytes, char *buf, size_t buflen, int *nsplit) {
+  if (!buf || buflen < 1) return SALUN_EINVAL;
+  buf[0] = 0;
+  if (nsplit) *nsplit = 0;
+  const bool w_al16 = !(flags & SALUN_ROUTE_W_UNALIGNED), out_al16 = !(flags & SALUN_ROUTE_OUT_UNALIGNED);
+  const bool in_al16 = !(flags & SALUN_ROUTE_IN_UNALIGNED);
+  int rc = SALUN_EINVAL, len = 0;
+  if (direction == SALUN_ROUTE_FORWARD) {
+    const DataPlan p = plan_data(N, C, K, P, Q, R, stride, false, C, (flags & SALUN_ROUTE_EPI) != 0, w_al16, out_al16,
+                                 ws_bytes);
+    if ((rc = p.rc) == SALUN_OK) len = data_label(buf, buflen, p);
+  } else if (direction == SALUN_ROUTE_BACKWARD_DATA && (P < 1 || Q < 1)) {
+  } else if (direction == SALUN_ROUTE_BACKWARD_DATA && stride == 1) {
+    const DataPlan p = plan_data(N, K, C, H, W, R, 1, true, C, false, w_al16, out_al16, ws_bytes);
+    if ((rc = p.rc) == SALUN_OK) len = data_label(buf, buflen, p);
+  } else if (direction == SALUN_ROUTE_BACKWARD_DATA && stride == 2) {
+    const Dgrad2Plan p = plan_dgrad_s2(N, C, H, W, K, R, pad, P, Q, w_al16, out_al16);
+    if ((rc = p.rc) == SALUN_OK) len = dgrad2_label(buf, buflen, p);
+  } else if (direction == SALUN_ROUTE_BACKWARD_WEIGHT) {
+    const WgradPlan p = plan_wgrad(N, C, H, W, K, R, stride, pad, P, Q, (flags & SALUN_WGRAD_SHARED) != 0, in_al16,
+                                   ws_bytes);
+    if ((rc = p.rc) == SALUN_OK) {
+      len = wgrad_label(buf, buflen, p);
+      if (nsplit) *nsplit = p.nsplit;
+    }
+  }
+  if (rc == SALUN_OK && (len < 0 || (size_t)len >= buflen)) { buf[0] = 0; return SALUN_ENOSPC; }
+  return rc;
 }

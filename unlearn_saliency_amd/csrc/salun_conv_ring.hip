@@ -24,6 +24,7 @@
 // (k-steps pair channels (2i, 2i+1) as before, in the same order), results are bit-identical to conv_igemm's.
 #include "salun_common.h"
 #include <mutex>
+#include <type_traits>
 #include <unordered_set>
 
 namespace {
@@ -668,34 +669,39 @@ int ring_dispatch(const RingArgs &a, int cfg, bool epi, int wgs_per_cu, hipStrea
 
 }  // namespace
 
-// Called by salun_conv2d_backward_weight (salun_conv.hip) for 3x3 / stride 1 / pad 1 layers before its own kernels:
-// SALUN_EINVAL = not this kernel's shape.  `part` = [nsplit][9][K][C], nchunks = 64-pixel chunks of the batch.
+// The backward-weight ring kernel's domain among 3x3 / stride 1 / pad 1 layers (a pure predicate: the backward-weight
+// plan of salun_conv.hip asks it, the launch below obeys it).  nchunks = 64-pixel chunks of the batch as the caller
+// counts them; in_al16 = x and dy on 16-byte boundaries.
+bool salun_ring_wgrad_fits(int N, int C, int H, int W, int K, int nchunks, bool in_al16) {
+  if (H != W || C % 64 != 0 || K % 32 != 0 || !in_al16) return false;
+  if ((long long)N * C * H * W >= (1ll << 31) || (long long)N * K * H * W >= (1ll << 31)) return false;
+  if (W != 4 && W != 8 && W != 16 && W != 32) return false;
+  const int NI = (W * W >= 64) ? 1 : 64 / (W * W);  // images per chunk (conv3x3_wgrad_ring<LOGW>)
+  return nchunks == ((NI > 1) ? (N + NI - 1) / NI : N * (W * W / 64));
+}
+
+// `part` = [nsplit][9][K][C].  SALUN_EINVAL = not this kernel's shape (salun_ring_wgrad_fits).
 int salun_ring_wgrad_launch(const float *x, const float *dy, float *part, int N, int C, int H, int W, int K, int nsplit,
                             int nchunks, hipStream_t st) {
-  if (H != W || C % 64 != 0 || K % 32 != 0 || !salun_aligned16(x) || !salun_aligned16(dy)) return SALUN_EINVAL;
-  if ((long long)N * C * H * W >= (1ll << 31) || (long long)N * K * H * W >= (1ll << 31)) return SALUN_EINVAL;
+  if (!salun_ring_wgrad_fits(N, C, H, W, K, nchunks, salun_aligned16(x) && salun_aligned16(dy))) return SALUN_EINVAL;
   const float *zero = ring_zero_page();
   if (!zero) return SALUN_EIO;
   WgradRingArgs a{x, dy, zero, part, N, C, K, nchunks};
   dim3 grid((K + 63) / 64, C / 64, nsplit);
-#define SALUN_WGR(LOGW_)                                                                                        \
-  {                                                                                                             \
-    constexpr int W_ = 1 << LOGW_, TP_ = (W_ * W_ >= 64) ? 64 / W_ : W_, NI_ = (W_ * W_ >= 64) ? 1 : 64 / (W_ * W_);  \
-    constexpr int PRX_ = (NI_ * (TP_ + 2) * (W_ / 4)) | 1;                                                      \
-    const size_t ldsb = 2 * (size_t)(64 * 17 * 16 + 64 * PRX_ * 16);                                            \
-    const int want = (NI_ > 1) ? (N + NI_ - 1) / NI_ : N * (W_ * W_ / 64);                                      \
-    if (want != nchunks) return SALUN_EINVAL;                                                                   \
-    ring_allow_lds(reinterpret_cast<const void *>(conv3x3_wgrad_ring<LOGW_>));                                  \
-    hipLaunchKernelGGL((conv3x3_wgrad_ring<LOGW_>), grid, dim3(256), ldsb, st, a);                              \
-  }
+  auto launch = [&](auto logw) {
+    constexpr int LOGW = decltype(logw)::value;
+    constexpr int W_ = 1 << LOGW, TP_ = (W_ * W_ >= 64) ? 64 / W_ : W_, NI_ = (W_ * W_ >= 64) ? 1 : 64 / (W_ * W_);
+    constexpr int PRX_ = (NI_ * (TP_ + 2) * (W_ / 4)) | 1;
+    const size_t ldsb = 2 * (size_t)(64 * 17 * 16 + 64 * PRX_ * 16);
+    ring_allow_lds(reinterpret_cast<const void *>(conv3x3_wgrad_ring<LOGW>));
+    hipLaunchKernelGGL((conv3x3_wgrad_ring<LOGW>), grid, dim3(256), ldsb, st, a);
+  };
   switch (W) {
-    case 4: SALUN_WGR(2) break;
-    case 8: SALUN_WGR(3) break;
-    case 16: SALUN_WGR(4) break;
-    case 32: SALUN_WGR(5) break;
-    default: return SALUN_EINVAL;
+    case 4: launch(std::integral_constant<int, 2>{}); break;
+    case 8: launch(std::integral_constant<int, 3>{}); break;
+    case 16: launch(std::integral_constant<int, 4>{}); break;
+    default: launch(std::integral_constant<int, 5>{}); break;
   }
-#undef SALUN_WGR
   SALUN_LAUNCH_CHECK();
   return SALUN_OK;
 }

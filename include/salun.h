@@ -627,6 +627,27 @@ size_t salun_gemm_f32_workspace_bytes(const salun_gemm_job_t *jobs /*host*/, int
 int salun_gemm_f32(const salun_gemm_job_t *jobs /*host*/, int njobs, const salun_gemm_seg_t *segs /*host*/, int nsegs,
                    int batch_outer, int batch_inner, const int64_t *batch_strides /*host[6] or NULL*/,
                    double alpha, void *ws /*dev or NULL*/, size_t ws_bytes, salun_stream_t stream);
+/* The route one salun_gemm_f32 call takes, from the very plan the call launches from (no HIP call; pointers are read
+ * for null-ness and alignment only).  ws, ws_bytes: the workspace the call would pass (never dereferenced here; a NULL
+ * or not 4-byte aligned `ws` is no workspace, for the call and for the query alike).  Returns SALUN_OK, or what the call
+ * would return (SALUN_EINVAL: refused).
+ *   tile           64 or 128 (square block tile);  tiles: block tiles of all jobs (gridDim.x)
+ *   nsplit         split shares launched (1: every workgroup writes C itself); nsplit_wanted: what the shape alone
+ *                  asks for (salun_gemm_f32_workspace_bytes sizes that), declined when the workspace is too short
+ *   per segment    amode / bmode (0 scalar loads, 1 16-byte loads along k, 2 16-byte loads along the row index) and
+ *                  chunk0, the index of its first 16-deep chunk in its job's chunk list
+ *   per job        nchunks, per (chunks per split share), empty_shares (shares that start past the last chunk and
+ *                  write zeros), tile0 (first block tile), fast_tiles (tiles on the unguarded float4 loop) */
+typedef struct {
+  int32_t tile, nsplit, nsplit_wanted, njobs, nsegs;
+  int64_t tiles;
+  int32_t nchunks[SALUN_GEMM_MAX_JOBS], per[SALUN_GEMM_MAX_JOBS], empty_shares[SALUN_GEMM_MAX_JOBS];
+  int32_t tile0[SALUN_GEMM_MAX_JOBS], fast_tiles[SALUN_GEMM_MAX_JOBS];
+  int32_t amode[SALUN_GEMM_MAX_SEGS], bmode[SALUN_GEMM_MAX_SEGS], chunk0[SALUN_GEMM_MAX_SEGS];
+} salun_gemm_route_t;
+int salun_gemm_f32_route(const salun_gemm_job_t *jobs /*host*/, int njobs, const salun_gemm_seg_t *segs /*host*/, int nsegs,
+                         int batch_outer, int batch_inner, const int64_t *batch_strides /*host[6] or NULL*/,
+                         const void *ws /*dev or NULL*/, size_t ws_bytes, salun_gemm_route_t *out /*host*/);
 /* out[j] (+)= sum_i x[i * ld + j]: the bias gradient of a Linear layer (the reference: autograd's sum over the token
  * dimension behind nn.Linear).  Two deterministic stages (row slabs, then the slabs in index order). */
 size_t salun_colsum_f32_workspace_bytes(int64_t M, int N);

@@ -27,11 +27,10 @@ import torch
 
 import conv_ref_cpu as R
 import conv_routes as M
+from guarded_arena import GUARD, NAN_BITS, SENTINEL, Arena
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 4096
-NAN_BITS, SENTINEL = 0x7FC00000, 0x7FA5A5A5      # a quiet NaN; a NaN pattern no computation produces
 EINVAL = -22
 CASES = R.CASES
 _id = lambda c: c.id
@@ -54,51 +53,6 @@ def log(line):
     if d and os.path.isdir(d):
         with open(os.path.join(d, "conv_bounds_measured.txt"), "a") as f:
             f.write(line + "\n")
-
-
-class Arena:
-    """The tensors of one call inside one flat device allocation, each behind and before GUARD floats."""
-
-    def __init__(self):
-        self.parts, self.fills, self.n = {}, [], 0
-
-    def put(self, name, data=None, shape=None, out=False, skew=0):
-        """An input (data given), an output (shape given; filled with the sentinel) or an in-place output (both).
-        skew: floats off the 16-byte boundary."""
-        shape = tuple(data.shape) if data is not None else tuple(shape)
-        numel = 1
-        for s in shape:
-            numel *= s
-        start = self.n + GUARD + skew
-        end = (start + numel + 3) // 4 * 4
-        self.fills.append((self.n, end + GUARD, SENTINEL if out else NAN_BITS, start, data))
-        self.parts[name] = (start, numel, shape, out)
-        self.n = end + GUARD
-        return self
-
-    def upload(self):
-        host = torch.empty(self.n, dtype=torch.int32)
-        for lo, hi, bits, start, data in self.fills:
-            host[lo:hi] = bits
-            if data is not None:
-                host[start:start + data.numel()] = data.reshape(-1).float().view(torch.int32)
-        self.host, self.dev = host, host.cuda()
-        return self
-
-    def ptr(self, name):
-        return c_void_p(self.dev.data_ptr() + 4 * self.parts[name][0]) if name in self.parts else c_void_p(None)
-
-    def result(self, name):
-        """The output `name` on the host, after checking that nothing outside the outputs changed."""
-        torch.cuda.synchronize()
-        after = self.dev.cpu()
-        lo = 0
-        for start, numel, _, out in sorted(self.parts.values()) + [(self.n, 0, None, True)]:
-            if out:                                # everything between two outputs: inputs and all the guards
-                assert torch.equal(after[lo:start], self.host[lo:start]), "a guard or an input was written"
-                lo = start + numel
-        start, numel, shape, _ = self.parts[name]
-        return after[start:start + numel].view(torch.float32).view(shape)
 
 
 def same(got, want64):

@@ -40,6 +40,14 @@ class GemmJob(ctypes.Structure):
                 ("accumulate", ctypes.c_int32)]
 
 
+class GemmRoute(ctypes.Structure):
+    """salun_gemm_route_t"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("tile", "nsplit", "nsplit_wanted", "njobs", "nsegs")] + \
+               [("tiles", ctypes.c_int64)] + \
+               [(n, ctypes.c_int32 * 32) for n in ("nchunks", "per", "empty_shares", "tile0", "fast_tiles", "amode", "bmode",
+                                                   "chunk0")]
+
+
 class PackJob(ctypes.Structure):
     """salun_pack_job_t"""
     _fields_ = [("w", c_void_p), ("img_fwd", c_void_p), ("img_dgrad", c_void_p), ("K", ctypes.c_int32),
@@ -154,6 +162,8 @@ SIGNATURES = {
                                                   c_int]),
     "salun_gemm_f32": (c_int, [ctypes.POINTER(GemmJob), c_int, ctypes.POINTER(GemmSeg), c_int, c_int, c_int,
                                ctypes.POINTER(c_int64), c_double, c_void_p, c_size_t, c_void_p]),
+    "salun_gemm_f32_route": (c_int, [ctypes.POINTER(GemmJob), c_int, ctypes.POINTER(GemmSeg), c_int, c_int, c_int,
+                                     ctypes.POINTER(c_int64), c_void_p, c_size_t, ctypes.POINTER(GemmRoute)]),
     "salun_colsum_f32_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "salun_colsum_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_int, c_void_p, c_size_t, c_void_p]),
     "salun_softmax_rows": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p]),

@@ -382,19 +382,61 @@ bool aligned16_stride(const void *p, long long bo, long long bi, int s) {
   return salun_aligned16(p) && (bo % 4 == 0) && (bi % 4 == 0) && (s % 4 == 0);
 }
 
-}  // namespace
+// 0 scalar, 1 16-byte loads along k (stride_k == 1), 2 16-byte loads along the row index
+int load_mode(const void *p, long long bo, long long bi, int s_row, int s_k) {
+  return (s_k == 1 && aligned16_stride(p, bo, bi, s_row)) ? 1 : (s_row == 1 && aligned16_stride(p, bo, bi, s_k)) ? 2 : 0;
+}
 
-// ================================================================== C-ABI =======
-static int gemm_tile_for(const salun_gemm_job_t *jobs, int njobs, int batch) {
-  // 128 x 128 block tiles when they alone fill the chip, else 64 x 64
+// 128 x 128 block tiles when they alone fill the chip, else 64 x 64
+int gemm_tile_for(const salun_gemm_job_t *jobs, int njobs, int batch) {
   long long t128 = 0;
   for (int j = 0; j < njobs; ++j) t128 += (long long)((jobs[j].M + 127) / 128) * ((jobs[j].N + 127) / 128);
   return (t128 * batch >= 512) ? 128 : 64;
 }
 
-static int gemm_plan(const salun_gemm_job_t *jobs, int njobs, const salun_gemm_seg_t *segs, int nsegs, int batch,
-                     int *tile_out, long long *tiles_out, int *split_out, long long *out_elems_out) {
-  if (!jobs || !segs || njobs < 1 || njobs > MAXJ || nsegs < 1 || nsegs > MAXS || batch < 1) return SALUN_EINVAL;
+// Everything the host decides about one call, decided once: the kernel arguments (all but alpha and the workspace
+// pointer), the grid, and the description of the route the workgroups will take (salun_gemm_f32_route hands it out).
+struct Plan {
+  Args a;
+  salun_gemm_route_t r;
+  long long out_elems;  // sum of M * N over the jobs
+  int batch;
+};
+
+// What the workgroups of k_gemm_f32 compute from `a`, restated per job: chunks per split share, shares left without a
+// chunk, tiles that take the FAST loop.
+void gemm_describe(Plan &p) {
+  const Args &a = p.a;
+  salun_gemm_route_t &r = p.r;
+  const int bt = r.tile;
+  for (int j = 0; j < a.njobs; ++j) {
+    const Job &J = a.job[j];
+    const int per = (J.nchunks + a.nsplit - 1) / a.nsplit;
+    int empty = 0;
+    for (int z = 0; z < a.nsplit; ++z) empty += (z * per >= J.nchunks);
+    bool vec = true;
+    for (int q = J.seg0; q < J.seg0 + J.nseg; ++q) {
+      const Seg &T = a.seg[q];
+      vec = vec && T.amode != 0 && T.bmode != 0 && T.K % BK == 0;
+      r.amode[q] = T.amode; r.bmode[q] = T.bmode; r.chunk0[q] = T.chunk0;
+    }
+    r.per[j] = per; r.nchunks[j] = J.nchunks; r.tile0[j] = J.tile0; r.empty_shares[j] = empty;
+    r.fast_tiles[j] = vec ? (J.M / bt) * (J.N / bt) : 0;
+  }
+}
+
+// a workspace pointer the split may use: the one test the call and the route query both apply
+bool gemm_ws_usable(const void *ws) { return ws && salun_aligned4(ws); }
+
+// No HIP call; pointers are read for null-ness and alignment only.  ws_ok: gemm_ws_usable(ws).
+int gemm_plan(const salun_gemm_job_t *jobs, int njobs, const salun_gemm_seg_t *segs, int nsegs, int batch_outer,
+              int batch_inner, const int64_t *batch_strides, bool ws_ok, size_t ws_bytes, Plan &p) {
+  if (batch_outer < 1 || batch_inner < 1) return SALUN_EINVAL;
+  const long long batch_ll = (long long)batch_outer * batch_inner;
+  if (batch_ll > 65535) return SALUN_EINVAL;
+  const int batch = (int)batch_ll;
+  if (batch > 1 && !batch_strides) return SALUN_EINVAL;
+  if (!jobs || !segs || njobs < 1 || njobs > MAXJ || nsegs < 1 || nsegs > MAXS) return SALUN_EINVAL;
   const int bt = gemm_tile_for(jobs, njobs, batch);
   long long tiles = 0, out_elems = 0;
   int min_chunks = 1 << 30;
@@ -410,6 +452,7 @@ static int gemm_plan(const salun_gemm_job_t *jobs, int njobs, const salun_gemm_s
     }
     if (chunks < min_chunks) min_chunks = chunks;
   }
+  if (tiles > 0x7fffffffLL) return SALUN_EINVAL;
   // split the reduction while the launch leaves the chip under-filled and every share keeps >= 4 chunks
   int split = 1;
   const long long wgs = tiles * batch;
@@ -418,43 +461,26 @@ static int gemm_plan(const salun_gemm_job_t *jobs, int njobs, const salun_gemm_s
     if (split > 16) split = 16;
     while (split > 1 && min_chunks / split < 4) --split;
   }
-  *tile_out = bt; *tiles_out = tiles; *split_out = split < 1 ? 1 : split; *out_elems_out = out_elems;
-  return SALUN_OK;
-}
-
-SALUN_EXPORT size_t salun_gemm_f32_workspace_bytes(const salun_gemm_job_t *jobs, int njobs, const salun_gemm_seg_t *segs,
-                                                   int nsegs, int batch_outer, int batch_inner) {
-  int bt, split;
-  long long tiles, out_elems;
-  if (batch_outer < 1 || batch_inner < 1) return 0;
-  if (gemm_plan(jobs, njobs, segs, nsegs, batch_outer * batch_inner, &bt, &tiles, &split, &out_elems) != SALUN_OK) return 0;
-  return split > 1 ? sizeof(float) * (size_t)split * (size_t)out_elems * (size_t)(batch_outer * batch_inner) : 0;
-}
-
-SALUN_EXPORT int salun_gemm_f32(const salun_gemm_job_t *jobs, int njobs, const salun_gemm_seg_t *segs, int nsegs,
-                                int batch_outer, int batch_inner, const int64_t *batch_strides /* a_bo a_bi b_bo b_bi c_bo c_bi */,
-                                double alpha, void *ws, size_t ws_bytes, salun_stream_t stream) {
-  if (batch_outer < 1 || batch_inner < 1) return SALUN_EINVAL;
-  const int batch = batch_outer * batch_inner;
-  if (batch > 1 && !batch_strides) return SALUN_EINVAL;
-  int bt, split;
-  long long tiles, out_elems;
-  const int rc = gemm_plan(jobs, njobs, segs, nsegs, batch, &bt, &tiles, &split, &out_elems);
-  if (rc != SALUN_OK) return rc;
-  if (batch > 65535 || tiles > 0x7fffffffLL) return SALUN_EINVAL;
+  if (split < 1) split = 1;
+  salun_gemm_route_t &r = p.r;
+  r = salun_gemm_route_t{};
+  r.tile = bt; r.tiles = tiles; r.njobs = njobs; r.nsegs = nsegs; r.nsplit_wanted = split;
   if (split > 1) {
     const size_t need = sizeof(float) * (size_t)split * (size_t)out_elems * (size_t)batch;
-    if (!ws || ws_bytes < need || !salun_aligned4(ws)) split = 1;  // no room: one workgroup per tile does the whole reduction
+    if (!ws_ok || ws_bytes < need) split = 1;  // no room: one workgroup per tile does the whole reduction
   }
-  Args a;
+  r.nsplit = split;
+  p.out_elems = out_elems;
+  p.batch = batch;
+  Args &a = p.a;
   a.njobs = njobs; a.nsplit = split; a.batch_inner = batch_inner;
   a.a_bo = a.a_bi = a.b_bo = a.b_bi = a.c_bo = a.c_bi = 0;
   if (batch_strides) {
     a.a_bo = batch_strides[0]; a.a_bi = batch_strides[1]; a.b_bo = batch_strides[2];
     a.b_bi = batch_strides[3]; a.c_bo = batch_strides[4]; a.c_bi = batch_strides[5];
   }
-  a.alpha = (float)alpha;
-  a.ws = static_cast<float *>(ws);
+  a.alpha = 1.f;
+  a.ws = nullptr;
   a.ws_batch = out_elems;
   a.ws_slab = out_elems * batch;
   long long tile0 = 0, ws_off = 0;
@@ -472,16 +498,51 @@ SALUN_EXPORT int salun_gemm_f32(const salun_gemm_job_t *jobs, int njobs, const s
       Seg &e = a.seg[s];
       e.A = S.A; e.B = S.B; e.K = S.K; e.a_i = S.a_i; e.a_k = S.a_k; e.b_j = S.b_j; e.b_k = S.b_k;
       e.chunk0 = chunk0; chunk0 += (S.K + BK - 1) / BK;
-      e.amode = (S.a_k == 1 && aligned16_stride(S.A, a.a_bo, a.a_bi, S.a_i)) ? 1
-              : (S.a_i == 1 && aligned16_stride(S.A, a.a_bo, a.a_bi, S.a_k)) ? 2 : 0;
-      e.bmode = (S.b_k == 1 && aligned16_stride(S.B, a.b_bo, a.b_bi, S.b_j)) ? 1
-              : (S.b_j == 1 && aligned16_stride(S.B, a.b_bo, a.b_bi, S.b_k)) ? 2 : 0;
+      e.amode = load_mode(S.A, a.a_bo, a.a_bi, S.a_i, S.a_k);
+      e.bmode = load_mode(S.B, a.b_bo, a.b_bi, S.b_j, S.b_k);
     }
     d.nchunks = chunk0;
   }
+  gemm_describe(p);
+  return SALUN_OK;
+}
+
+}  // namespace
+
+// ================================================================== C-ABI =======
+SALUN_EXPORT size_t salun_gemm_f32_workspace_bytes(const salun_gemm_job_t *jobs, int njobs, const salun_gemm_seg_t *segs,
+                                                   int nsegs, int batch_outer, int batch_inner) {
+  static const int64_t no_strides[6] = {0, 0, 0, 0, 0, 0};
+  Plan p;
+  if (gemm_plan(jobs, njobs, segs, nsegs, batch_outer, batch_inner, no_strides, false, 0, p) != SALUN_OK) return 0;
+  const int split = p.r.nsplit_wanted;
+  return split > 1 ? sizeof(float) * (size_t)split * (size_t)p.out_elems * (size_t)p.batch : 0;
+}
+
+SALUN_EXPORT int salun_gemm_f32_route(const salun_gemm_job_t *jobs, int njobs, const salun_gemm_seg_t *segs, int nsegs,
+                                      int batch_outer, int batch_inner, const int64_t *batch_strides, const void *ws,
+                                      size_t ws_bytes, salun_gemm_route_t *out) {
+  if (!out) return SALUN_EINVAL;
+  Plan p;
+  const int rc = gemm_plan(jobs, njobs, segs, nsegs, batch_outer, batch_inner, batch_strides, gemm_ws_usable(ws), ws_bytes, p);
+  if (rc != SALUN_OK) return rc;
+  *out = p.r;
+  return SALUN_OK;
+}
+
+SALUN_EXPORT int salun_gemm_f32(const salun_gemm_job_t *jobs, int njobs, const salun_gemm_seg_t *segs, int nsegs,
+                                int batch_outer, int batch_inner, const int64_t *batch_strides /* a_bo a_bi b_bo b_bi c_bo c_bi */,
+                                double alpha, void *ws, size_t ws_bytes, salun_stream_t stream) {
+  Plan p;
+  const int rc = gemm_plan(jobs, njobs, segs, nsegs, batch_outer, batch_inner, batch_strides, gemm_ws_usable(ws), ws_bytes, p);
+  if (rc != SALUN_OK) return rc;
+  Args &a = p.a;
+  a.alpha = (float)alpha;
+  a.ws = static_cast<float *>(ws);
+  const int split = p.r.nsplit, batch = p.batch;
   hipStream_t st = salun_hip_stream(stream);
-  const dim3 grid((unsigned)tiles, (unsigned)batch, (unsigned)split);
-  if (bt == 128) hipLaunchKernelGGL(k_gemm_f32<2>, grid, dim3(256), 0, st, a);
+  const dim3 grid((unsigned)p.r.tiles, (unsigned)batch, (unsigned)split);
+  if (p.r.tile == 128) hipLaunchKernelGGL(k_gemm_f32<2>, grid, dim3(256), 0, st, a);
   else hipLaunchKernelGGL(k_gemm_f32<1>, grid, dim3(256), 0, st, a);
   SALUN_LAUNCH_CHECK();
   if (split > 1) {

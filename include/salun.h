@@ -892,6 +892,43 @@ int salun_prune_status(const void *ws /*dev*/, int64_t n_sel, int ranked, int *r
 int salun_prune_count_zeros(const float *p /*dev*/, int64_t n, const int64_t *segs /*dev, 2 * nseg*/, int nseg,
                             int64_t n_sel, int64_t *count /*dev*/, salun_stream_t stream);
 
+/* ----------------------------------------------------------------- K23 --
+ * The fused classifier head (csrc/salun_cls_head.hip), fp32.
+ * Replaces  AdaptiveAvgPool2d((1, 1)) -> flatten -> nn.Linear -> CrossEntropyLoss() -> utils.accuracy / AverageMeter
+ *   Classification/models/ResNet.py:317-320, Classification/trainer/train.py:97-117  and their backward.
+ * x [B, C, HW] (NCHW, contiguous), w [K, C], bias [K], labels [B] int64.
+ *   pooled[b, c] = mean_hw x        logits[b, k] = bias[k] + sum_c pooled[b, c] w[k, c]
+ *   p = softmax(logits) (maximum subtracted)          loss[b] = -log p[b, labels[b]]
+ *   hit_b = (lowest index of the row's maximum == labels[b])
+ * Forward: one memset (a 4-byte ticket in ws) and ONE launch.  It writes pooled, logits, p and loss[B], and — each
+ * may be NULL — adds sum_b loss[b] (float64, fixed order) to *loss_sum, the number of hits to *hits and B to *count
+ * (caller-owned running meters: no host synchronisation, no meter kernels), and writes the batch mean to *loss_mean.
+ * ws is needed (salun_cls_head_workspace_bytes) when any of the four is given.
+ * Backward: two launches.  scale = *grad_out / B (grad_out NULL: 1);
+ *   dlogits[b, k] = (p[b, k] - [k == labels[b]]) * scale        dx[b, c, :] = (sum_k dlogits[b, k] w[k, c]) / HW
+ *   dw[k, c] (+)= sum_b dlogits[b, k] pooled[b, c]               db[k] (+)= sum_b dlogits[b, k]
+ * dx, dw, db may each be NULL (not computed); accumulate_w / accumulate_b != 0 add into dw / db.
+ * A label outside [0, K) causes no out-of-range access: that sample's loss and its dlogits / dx rows are NaN, its hit
+ * is 0, it counts in *count; the NaN reaches the sums (loss_sum, loss_mean, dw, db).
+ * No floating-point atomics: every reduction has one order fixed by the shape, results are bit-identical run to run.
+ * SALUN_EINVAL: B < 1, C outside [1, SALUN_CLS_HEAD_MAX_C], HW < 1, K outside [1, SALUN_CLS_HEAD_MAX_K] (the per-sample
+ * rows live in LDS), a NULL required pointer, a pointer off its element's alignment (4 bytes; 8 for labels, loss_sum,
+ * hits, count).  float4 loads / stores of x / dx are used when they are 16-byte aligned and HW % 4 == 0. */
+#define SALUN_CLS_HEAD_MAX_C 8192
+#define SALUN_CLS_HEAD_MAX_K 1024
+size_t salun_cls_head_workspace_bytes(int64_t B, int C, int K);
+int salun_cls_head_forward(const float *x /*dev*/, const float *w /*dev*/, const float *bias /*dev*/,
+                           const int64_t *labels /*dev*/, float *pooled /*dev, B*C*/, float *logits /*dev, B*K*/,
+                           float *p /*dev, B*K*/, float *loss /*dev, B*/, float *loss_mean /*dev, 1, or NULL*/,
+                           double *loss_sum /*dev or NULL*/, int64_t *hits /*dev or NULL*/,
+                           int64_t *count /*dev or NULL*/, int64_t B, int C, int HW, int K, void *ws /*dev*/,
+                           size_t ws_bytes, salun_stream_t stream);
+int salun_cls_head_backward(const float *p /*dev*/, const float *pooled /*dev*/, const float *w /*dev*/,
+                            const int64_t *labels /*dev*/, const float *grad_out /*dev, 1, or NULL*/,
+                            float *dlogits /*dev, B*K*/, float *dx /*dev or NULL*/, float *dw /*dev or NULL*/,
+                            float *db /*dev or NULL*/, int accumulate_w, int accumulate_b, int64_t B, int C, int HW,
+                            int K, salun_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -100,16 +100,26 @@ class ResNetCifar(nn.Module):
                 nn.init.zeros_(mod.bias)
 
     fused_bn = False
+    fused_head = False  # set by unlearn_saliency_amd.cls_head.use_fused_head
 
-    def forward(self, x):
+    def features(self, x):
+        """layer4's output [B, C, H, W]: what the average pool of the head reads."""
         x = self.normalize(x)
         if self.fused_bn:
             from ...norm import fused_bn_act
             x = self.maxpool(fused_bn_act(self.conv1(x), self.bn1, relu=True))
         else:
             x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
-        x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
-        return self.fc(torch.flatten(self.avgpool(x), 1))
+        return self.layer4(self.layer3(self.layer2(self.layer1(x))))
+
+    def forward(self, x):
+        return self.fc(torch.flatten(self.avgpool(self.features(x)), 1))
+
+    def forward_loss(self, x, target, meters=None):
+        """(mean cross-entropy, logits.detach()) of a batch; with `use_fused_head` the head is K23
+        (csrc/salun_cls_head.hip), which also adds the batch's loss sum / hits / count to `meters` on the device."""
+        from ...cls_head import forward_loss
+        return forward_loss(self, x, target, meters)
 
 
 def resnet18(num_classes: int = 10, imagenet: bool = False, **_unused) -> ResNetCifar:

@@ -1,4 +1,4 @@
-"""Evaluation loop used for the UA/RA/TA accuracies.  (The reference's trainer package also
-exports pre-training loops — out of scope, SURVEY.md §2 C8 — and a `train_with_rewind` that
-does not exist upstream; neither is reproduced.)"""
+"""The pre-training epoch and the evaluation loop used for the UA/RA/TA accuracies.  (The reference's trainer package
+also exports a `train_with_rewind` that does not exist upstream; it is not reproduced.)"""
+from .train import get_optimizer_and_scheduler, train
 from .val import validate

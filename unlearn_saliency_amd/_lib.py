@@ -63,6 +63,8 @@ class Bf16PackJob(ctypes.Structure):
 SALUN_BF16_PACK_MAX_JOBS = 64
 SALUN_GEMM_MAX_JOBS = 32
 SALUN_GEMM_MAX_SEGS = 32
+SALUN_CLS_HEAD_MAX_C = 8192
+SALUN_CLS_HEAD_MAX_K = 1024
 
 # name -> (restype, argtypes); mirrors include/salun.h one to one
 # (tests/test_cabi.py checks this table against the header and the .so).
@@ -210,6 +212,9 @@ SIGNATURES = {
                                    c_void_p, ctypes.c_uint, c_void_p, c_size_t, c_void_p]),
     "salun_prune_status": (c_int, [c_void_p, c_int64, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_void_p]),
     "salun_prune_count_zeros": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int64, c_void_p, c_void_p]),
+    "salun_cls_head_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "salun_cls_head_forward": (c_int, [c_void_p] * 12 + [c_int64, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "salun_cls_head_backward": (c_int, [c_void_p] * 9 + [c_int, c_int, c_int64, c_int, c_int, c_int, c_void_p]),
 }
 
 _lib = None

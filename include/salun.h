@@ -429,6 +429,24 @@ int salun_conv2d_bf16_backward_weight_ex(const uint16_t *x /*dev*/, const uint16
                                          float *db /*dev or NULL*/, float *dnb /*dev or NULL*/, int N, int H, int W, int C,
                                          int K, int R, int stride, int pad, int accumulate, void *ws /*dev*/,
                                          size_t ws_bytes, salun_stream_t stream);
+/* Which kernel, tile and split a call of this family runs (as salun_conv2d_route for the fp32 family): the label of the
+ * plan salun_conv2d_bf16_forward / _backward_data / _backward_weight_ex would execute, from the plan functions they launch
+ * from (csrc/salun_bf16_plan.h).  Touches no device.  Returns SALUN_OK, or what the entry point would return for the shape
+ * (SALUN_EINVAL: refused; backward-weight with `ws_bytes` short of salun_conv2d_bf16_wgrad_workspace_bytes: SALUN_ENOSPC).
+ *   direction  SALUN_ROUTE_FORWARD, SALUN_ROUTE_BACKWARD_DATA or SALUN_ROUTE_BACKWARD_WEIGHT
+ *   flags      SALUN_ROUTE_OUT_UNALIGNED: forward - y, bias, nbias or addend, backward-weight - dw off a 16-byte boundary;
+ *              SALUN_ROUTE_EPI is accepted and changes no plan (both forward kernels carry every epilogue term);
+ *              SALUN_ROUTE_RING(v) / SALUN_ROUTE_WGRAD_TN(v): plan as a process started with SALUN_CONV_RING=v (0..3) /
+ *              SALUN_WGRAD_TN=v (0, 1) would - without them the query reads the process's switches, as the launch does
+ *   ws_bytes   of the workspace the call would pass (0: none - the data kernels then do not split)
+ *   nsplit     (optional) the reduction splits of the plan (1: none)
+ * Labels: ring<WGM,WGN,NST>, igemm<WM,WN,BK[,dgrad]>/S<split>, wgrad_tn<v<variant>>/S<split>, wgrad_tap<R,stride>/S<split>. */
+#define SALUN_ROUTE_RING_SHIFT 8
+#define SALUN_ROUTE_RING(v) ((unsigned)((v) + 1) << SALUN_ROUTE_RING_SHIFT)
+#define SALUN_ROUTE_WGRAD_TN_SHIFT 12
+#define SALUN_ROUTE_WGRAD_TN(v) ((unsigned)((v) + 1) << SALUN_ROUTE_WGRAD_TN_SHIFT)
+int salun_conv2d_bf16_route(int direction, int N, int H, int W, int C, int K, int R, int stride, int pad, unsigned flags,
+                            size_t ws_bytes, char *buf, size_t buflen, int *nsplit /*or NULL*/);
 
 /* ------------------------------------------------------------------ K12 --
  * GroupNorm (+ SiLU) on bf16 NHWC activations with fp32 statistics — the `GroupNorm32` layers of the SD U-Net in its
@@ -668,7 +686,10 @@ int salun_softmax_rows_backward(const float *p /*dev*/, float *dp /*dev*/, int64
  * x, w, addend, y: bf16 row-major; both operand tiles go global -> LDS directly (global_load_lds_dwordx4, bank swizzle on
  * the source address).  The input gradient dX = dY . W is the same call on the transposed image (salun_pack_bf16 with
  * transposed = 1).  Requirements: K % 64 == 0, N % 64 == 0, 16-byte aligned pointers (salun_gemm_bf16_supported);
- * SALUN_EINVAL otherwise.  variant: 0 = choose the tile, 1..4 = pin one (A/B measurements). */
+ * SALUN_EINVAL otherwise.  variant: 0 = choose the tile; 1..13 pin one (A/B measurements): 1 / 2 = 128 tokens x 128
+ * features double- / single-buffered, 3 / 4 = 256 x 64 likewise, 5 / 6 = the persistent forms of 1 / 3, 7..13 = the LDS ring
+ * (128 x 128 x 4 stages, 256 x 128 x 3, 256 x 64 x 3, 128 x 128 x 3, and 11..13 = 8 / 7 / 9 with 32-deep stages).  The
+ * 128-feature tiles (1, 2, 5, 7, 8, 10, 11, 12) need N % 128 == 0. */
 int salun_gemm_bf16_supported(int64_t M, int N, int K);
 int salun_gemm_bf16_nt(const void *x /*dev bf16*/, const void *w /*dev bf16*/, const float *bias /*dev or NULL*/,
                        const void *addend /*dev bf16 or NULL*/, void *y /*dev bf16*/, int64_t M, int N, int K,
@@ -678,11 +699,19 @@ int salun_gemm_bf16_nt(const void *x /*dev bf16*/, const void *w /*dev bf16*/, c
  * the layers above).  The reduction index M is the slow axis of both operands: tiles go global -> LDS directly and the
  * MFMA operands are gathered with transposing LDS reads.  Split over M into partials in `ws`
  * (salun_gemm_bf16_tn_workspace_bytes) folded in index order — deterministic.  Na, Nb multiples of 32, M < 2^24.
- * variant: 0 = choose, 1..3 = pin a tile (A/B measurements). */
+ * variant: 0 = choose (2); 1 = 128 x 128 tile, 64-token stages, 2 = 128 x 128, 32-token stages, 3 = 256 x 128, 64-token
+ * stages (A/B measurements). */
 int salun_gemm_bf16_tn_supported(int64_t M, int Na, int Nb);
 size_t salun_gemm_bf16_tn_workspace_bytes(int64_t M, int Na, int Nb, int variant);
 int salun_gemm_bf16_tn(const void *dy /*dev bf16*/, const void *x /*dev bf16*/, float *dw /*dev*/, int64_t M, int Na, int Nb,
                        int accumulate, int variant, void *ws /*dev or NULL*/, size_t ws_bytes, salun_stream_t stream);
+/* The plan of salun_gemm_bf16_nt (op = SALUN_GEMM_BF16_NT; `ws_bytes` unused) or of salun_gemm_bf16_tn (op =
+ * SALUN_GEMM_BF16_TN with (M, N, K) = (M, Na, Nb)) as a label, as salun_conv2d_bf16_route: host only; SALUN_OK or what the
+ * entry point would return.  Labels: nt<WGM,WGN,db|sb>, nt_p<WGM,WGN>, nt_r<WGM,WGN,NST,BK>, tn<v<variant>>/S<split>. */
+#define SALUN_GEMM_BF16_NT 0
+#define SALUN_GEMM_BF16_TN 1
+int salun_gemm_bf16_route(int op, int64_t M, int N, int K, int variant, size_t ws_bytes, char *buf, size_t buflen,
+                          int *nsplit /*or NULL*/);
 /* fp32 master weights w[N][K] -> the bf16 image the GEMM reads: [N][K] (transposed = 0) or [K][N] (transposed = 1).
  * Once per optimizer step per layer. */
 int salun_pack_bf16(const float *w /*dev*/, void *wp /*dev bf16*/, int N, int K, int transposed, salun_stream_t stream);

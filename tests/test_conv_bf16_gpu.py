@@ -79,7 +79,9 @@ def test_forward_backward_match_library_on_bf16_inputs(shape):
 
 
 # (N, H, W, C, K): 64 channels -> the reduction is split and k_splitk_finish carries the terms; 32 channels -> nine stages,
-# no split: conv_bf16_igemm's own epilogue (ragged pixel and channel tiles in the second case)
+# no split: conv_bf16_igemm's own epilogue (ragged pixel and channel tiles in the third case).  Forward reduces over C,
+# backward-data over K: the first case splits both, the second neither, the last two backward-data only
+# (test_bf16_routes_cpu.py::test_routes_the_gpu_tests_claim)
 @pytest.mark.parametrize("dims", [(2, 8, 8, 64, 64), (2, 8, 8, 32, 32), (1, 5, 7, 32, 96), (3, 16, 16, 32, 160)])
 def test_epilogue_terms(dims):
     from unlearn_saliency_amd import ops
@@ -98,14 +100,59 @@ def test_epilogue_terms(dims):
     _close_bf16(dx1, dx_ref.permute(0, 2, 3, 1) + addx.float(), "backward-data + addend")
 
 
+def _route(direction, shape, flags=0, ws_bytes=0):
+    """salun_conv2d_bf16_route: (label, splits) of the plan the matching entry point would execute (0 / 1 / 2 = forward /
+    backward-data / backward-weight)"""
+    import ctypes
+    from unlearn_saliency_amd import _lib
+    buf, ns = ctypes.create_string_buffer(64), ctypes.c_int(0)
+    _lib.check(_lib.lib().salun_conv2d_bf16_route(direction, *shape, flags, ws_bytes, buf, 64, ctypes.byref(ns)),
+               "salun_conv2d_bf16_route")
+    return buf.value.decode(), ns.value
+
+
+def test_a_missing_or_short_workspace_only_disables_the_split():
+    """One 128 x 128 tile, 18 stages: with the queried workspace (3 fp32 copies of the 128 x 64 output) the reduction
+    runs in 3 splits, with a NULL workspace or one a byte short in one - and gives the same convolution."""
+    from ctypes import c_size_t, c_void_p
+    from unlearn_saliency_amd import _lib, ops
+    shape = N, H, W, C, K, R, st, pad = (2, 8, 8, 64, 64, 3, 1, 1)
+    L = _lib.lib()
+    need = L.salun_conv2d_bf16_data_workspace_bytes(*shape)
+    assert need == 3 * (N * H * W) * K * 4 == 98304
+    x, dy = _mk((N, H, W, C), 1), _mk((N, H, W, K), 3)
+    w = torch.randn(K, C, R, R, device="cuda", generator=torch.Generator(device="cuda").manual_seed(2)) / (C * R * R) ** 0.5
+    wp, w_r = ops.conv2d_bf16_pack(w), w.to(torch.bfloat16).float()
+    ref_y = torch.nn.functional.conv2d(x.float().permute(0, 3, 1, 2), w_r, None, st, pad).permute(0, 2, 3, 1)
+    ref_dx = torch.nn.functional.conv_transpose2d(dy.float().permute(0, 3, 1, 2), w_r, None, st, pad).permute(0, 2, 3, 1)
+    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+    # (pointer, bytes the call states, bytes the query is asked about, splits)
+    for what, ptr, nbytes, asked, splits in (("queried", ws.data_ptr(), need, need, 3), ("NULL", None, need, 0, 1),
+                                             ("one byte short", ws.data_ptr(), need - 1, need - 1, 1)):
+        assert _route(0, shape, 0, asked) == ("igemm<2,2,32>/S%d" % splits, splits)
+        assert _route(1, shape, 0, asked) == ("igemm<2,2,32,dgrad>/S%d" % splits, splits)
+        y, dx = torch.empty((N, H, W, K), dtype=torch.bfloat16, device="cuda"), torch.empty_like(x)
+        _lib.check(L.salun_conv2d_bf16_forward(x.data_ptr(), wp.data_ptr(), None, None, None, y.data_ptr(), *shape,
+                                               c_void_p(ptr), c_size_t(nbytes), ops._stream()), "salun_conv2d_bf16_forward")
+        _lib.check(L.salun_conv2d_bf16_backward_data(dy.data_ptr(), wp.data_ptr(), None, dx.data_ptr(), *shape,
+                                                     c_void_p(ptr), c_size_t(nbytes), ops._stream()),
+                   "salun_conv2d_bf16_backward_data")
+        _close_bf16(y, ref_y, "forward, %s workspace" % what)
+        _close_bf16(dx, ref_dx, "backward-data, %s workspace" % what)
+
+
 def test_ring_kernel_every_tile_form_in_a_child_process():
     """SALUN_CONV_RING=3 sends every eligible forward launch (>= 128 tiles) to the LDS-DMA ring kernel (by default only the
     1x1 convolutions go there: the 3x3 ones are faster on the register-staged kernel); the switch is read once per process,
-    so the 3x3 / stride-2 / ragged shapes of SHAPES and the epilogue terms are re-run in a child."""
+    so the 3x3 / stride-2 / ragged shapes of SHAPES and the epilogue terms are re-run in a child - which first asks the route
+    query, without an override, that its switch took: the query and the launch read the same one."""
     import os, subprocess, sys
     here = os.path.dirname(os.path.abspath(__file__))
     code = ("import sys, torch; sys.path.insert(0, %r); import test_conv_bf16_gpu as t\n"
             "from unlearn_saliency_amd import ops\n"
+            "for sh in t.SHAPES[-4:]:\n"
+            "    ws = ops._q('salun_conv2d_bf16_data_workspace_bytes', *sh)\n"
+            "    assert t._route(0, sh, 0, ws)[0].startswith('ring<'), (sh, t._route(0, sh, 0, ws))\n"
             "for sh in t.SHAPES[-4:] + [(8, 32, 32, 320, 320, 3, 1, 1), (8, 16, 16, 640, 1280, 3, 1, 1)]:\n"
             "    t.test_forward_backward_match_library_on_bf16_inputs(sh)\n"
             "N,H,W,C,K=4,64,64,64,256; x=t._mk((N,H,W,C),5); w=torch.randn(K,C,3,3,device='cuda')/24.0\n"

@@ -145,7 +145,8 @@ def test_gemm_bf16_tn_weight_gradient_matches_fp32_matmul_of_the_rounded_operand
 
 
 def test_conv_1x1_and_linear_weight_gradients_take_the_tn_kernel_and_agree_with_the_tap_kernel():
-    """salun_conv2d_bf16_backward_weight routes 1x1 / stride 1 / no padding to the TN GEMM; the bias gradient rides along."""
+    """salun_conv2d_bf16_backward_weight routes 1x1 / stride 1 / no padding with >= 1024 pixels to the TN GEMM (this case has
+    512: the 1x1 tap kernel, test_bf16_routes_cpu.py); the bias gradient rides along."""
     from unlearn_saliency_amd import ops
     N, H, W, C, K = 2, 16, 16, 320, 640
     x, dy = dev((N, H, W, C), 21).bfloat16(), dev((N, H, W, K), 22).bfloat16()
@@ -158,3 +159,26 @@ def test_conv_1x1_and_linear_weight_gradients_take_the_tn_kernel_and_agree_with_
     dw2 = dw.clone()
     ops.conv2d_bf16_backward_weight(x, dy, (K, C, 1, 1), 1, 0, out=dw2, accumulate=True)
     assert rel(dw2, 2 * dw.double()) <= 2e-6
+
+
+def test_an_unaligned_weight_gradient_takes_the_tap_kernel_and_an_aligned_one_the_tn_gemm():
+    """1024 tokens, the fewest the TN route takes: a gradient 4 bytes past a 16-byte boundary (behind an odd-sized parameter
+    of the flat arena) goes to the tap kernel, an aligned one to the GEMM; same product, bias gradient on both."""
+    from test_conv_bf16_gpu import _route
+    from unlearn_saliency_amd import ops
+    N, H, W, C, K = 1, 32, 32, 64, 64
+    shape = (N, H, W, C, K, 1, 1, 0)
+    ws = ops._q("salun_conv2d_bf16_wgrad_workspace_bytes", *shape)
+    assert _route(2, shape, 0, ws)[0].startswith("wgrad_tn<v2>/") and _route(2, shape, 8, ws)[0].startswith("wgrad_tap<1,1>/")
+    x, dy = dev((N, H, W, C), 31).bfloat16(), dev((N, H, W, K), 32).bfloat16()
+    want = dy.view(-1, K).double().t() @ x.view(-1, C).double()
+    want_db = dy.view(-1, K).double().sum(0)
+    arena = torch.zeros(K * C + 4, device="cuda")
+    assert arena.data_ptr() % 16 == 0
+    for off in (0, 1):
+        out = arena[off:off + K * C].view(K, C, 1, 1)
+        assert out.data_ptr() % 16 == 4 * off
+        db = torch.zeros(K, device="cuda")
+        ops.conv2d_bf16_backward_weight(x, dy, (K, C, 1, 1), 1, 0, out=out, bias_out=db)
+        assert rel(out.view(K, C), want) <= 2e-6, off
+        assert rel(db, want_db) <= 2e-6, off

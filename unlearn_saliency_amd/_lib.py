@@ -135,6 +135,8 @@ SIGNATURES = {
     "salun_colsum_bf16_workspace_bytes": (c_size_t, [c_int]),
     "salun_colsum_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "salun_conv2d_bf16_backward_weight_ex": (c_int, [c_void_p] * 5 + [c_int] * 9 + [c_void_p, c_size_t, c_void_p]),
+    "salun_conv2d_bf16_route": (c_int, [c_int] * 9 + [ctypes.c_uint, c_size_t, ctypes.c_char_p, c_size_t,
+                                        ctypes.POINTER(c_int)]),
     "salun_gn_bf16_workspace_bytes": (c_size_t, [c_int] * 4),
     "salun_gn_bf16_forward": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_double, c_int, c_void_p, c_size_t, c_void_p]),
     "salun_gn_bf16_backward": (c_int, [c_void_p] * 8 + [c_int] * 6 + [c_void_p, c_size_t, c_void_p]),
@@ -176,6 +178,8 @@ SIGNATURES = {
     "salun_gemm_bf16_tn_supported": (c_int, [c_int64, c_int, c_int]),
     "salun_gemm_bf16_tn_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int]),
     "salun_gemm_bf16_tn": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "salun_gemm_bf16_route": (c_int, [c_int, c_int64, c_int, c_int, c_int, c_size_t, ctypes.c_char_p, c_size_t,
+                                      ctypes.POINTER(c_int)]),
     "salun_dropout": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_double, c_uint64, c_void_p, c_void_p]),
     "salun_u64_add": (c_int, [c_void_p, c_uint64, c_void_p]),
     "salun_iu_dot_workspace_bytes": (c_size_t, [c_int, c_int64]),

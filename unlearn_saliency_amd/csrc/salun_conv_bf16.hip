@@ -23,12 +23,7 @@
 //
 // Workgroup = 4 or 8 waves, each wave a 64x64 result tile (2x2 MFMA tiles, 64 fp32 accumulators); LDS double
 // buffered, global loads of stage i+1 in flight under the MFMAs of stage i, one barrier per stage.
-#include "salun_common.h"
-#include <cstdlib>
-
-#ifndef SALUN_BF16_TILE
-#define SALUN_BF16_TILE 0  // lab builds (tools/_run_bf16_lab.sh) pin one tile shape; 0 = choose per problem
-#endif
+#include "salun_bf16_internal.h"
 
 namespace {
 
@@ -738,7 +733,6 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce_bf16(const float *__restri
 
 // per-channel sum over pixels of an NHWC bf16 tensor (the bias gradient): [M][K] -> fp32 [K], two deterministic stages.
 // Stage 1: block = 32 channel groups (8 channels each, one 16-byte load) x 8 row lanes over one row chunk.
-constexpr int COLSUM_CHUNKS = 128;
 // With `cpi` chunks per image (rows_per_image = OH * OW) no chunk straddles two images, and the finish kernel can also give
 // the per-image sums dnb[n][k] — the gradient of the per-image channel offset `nbias` of the forward epilogue (a ResBlock's
 // time-embedding term), which was a bf16 -> fp32 copy of dy plus a library reduction per ResBlock convolution before round 6.
@@ -827,129 +821,53 @@ int launch_colsum(const uint16_t *dy, float *cpart, float *db, float *dnb, int64
   return SALUN_OK;
 }
 
-#ifndef SALUN_BF16_WGRAD_TARGET
-#define SALUN_BF16_WGRAD_TARGET 384  // lab builds: other split targets (profiles/r05_wgrad_phases.txt, table 2)
-#endif
-int wgrad_splits(int tiles, int chunks) {
-  // about 1.5 workgroups per CU, never more splits than chunks
-  // measured on the SD-v1 step (round 3, one box, four builds): 1536 / 768 / 384 / 256 target workgroups ->
-  // 219.3 / 209.3 / 205.7 / 206.6 ms; again with the paired 3x3 kernel (round 5, layer table): 512 / 384 / 256 ->
-  // 2.39 / 1.99 / 2.08 ms — every split adds a K*C*R*R fp32 partial to write and re-read (59 MB for a
-  // 1280x1280 3x3 layer), which costs more than the second resident round of workgroups gives back
-  int s = (SALUN_BF16_WGRAD_TARGET + tiles - 1) / tiles;
-  if (s > chunks) s = chunks;
-  if (s > 64) s = 64;
-  if (s < 1) s = 1;
-  return s;
-}
-
-// (The kernels lean on this domain: aim_tap's `tap / 3` as (tap * 11) >> 5 is exact for tap < 9 only, i.e. R in {1, 3}, and
-// the backward-weight epilogue guards whole waves with K % 32 == 0.  Widening it means revisiting both — ADVICE r5.)
-bool supported(int C, int K, int R, int stride, int pad) {
-  return (R == 1 || R == 3) && (stride == 1 || stride == 2) && pad >= 0 && pad <= R - 1 && C % 32 == 0 && K % 32 == 0 &&
-         C >= 32 && K >= 32;
-}
-
-// Reduction split of the data kernels: a convolution with few output tiles (the 16x16 and 8x8 levels of the U-Net)
-// leaves most CUs without a workgroup, and a lone workgroup pays the full memory latency on every stage; splitting
-// the (tap, channel) reduction over blockIdx.z fills the chip (target: 3 workgroups per CU) at the price of one fp32
-// round trip of the output tile.
-#ifndef SALUN_BF16_SPLIT_TARGET
-#define SALUN_BF16_SPLIT_TARGET 768  // lab builds: other targets (profiles/r06_sd_split_targets.txt)
-#endif
-struct SplitPlan { int splits, per; };
-SplitPlan plan_split(int tiles, int nstage) {
-  int s = SALUN_BF16_SPLIT_TARGET / (tiles < 1 ? 1 : tiles);
-  if (s > nstage / 6) s = nstage / 6;  // at least 6 stages per workgroup
-  if (s > 16) s = 16;
-  if (s < 1) s = 1;
-  const int per = (nstage + s - 1) / s;
-  s = (nstage + per - 1) / per;
-  return {s, per};
-}
-
+// conv_bf16_igemm<WM, WN, BK, BTR> (and k_splitk_finish behind a split reduction) as the plan says
 template <int WM, int WN, int BK, bool BTR>
-int launch_igemm(IgArgs a, void *ws, size_t ws_bytes, hipStream_t st) {
+int launch_igemm(const ConvDataPlan &p, IgArgs a, void *ws, hipStream_t st) {
   constexpr int BM = 64 * WM, BN = 64 * WN;
   constexpr int ROWB = BK * 2 + 16;
   constexpr int A_BYTES = BM * ROWB;
   constexpr int B_BYTES = BTR ? (BN / 32) * (BK * 64) : BN * ROWB;
-  const size_t lds = 2 * (size_t)(A_BYTES + B_BYTES);
-  static unsigned long long attr_done = 0;  // one bit per device
-  if (salun_once_needed(&attr_done)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_bf16_igemm<WM, WN, BK, BTR>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return SALUN_EIO;
-    salun_once_mark(&attr_done);
-  }
-  const int mt = (a.M + BM - 1) / BM, nt = (a.Kout + BN - 1) / BN;
-  const int nstage = a.R * a.R * (a.Cin / BK);
-  SplitPlan sp = plan_split(mt * nt, nstage);
-  if (sp.splits > 1 && (!ws || ws_bytes < (size_t)sp.splits * a.M * a.Kout * sizeof(float))) sp = {1, nstage};
-  a.stages_per_split = sp.per;
-  a.part = sp.splits > 1 ? static_cast<float *>(ws) : nullptr;
-  {  // buffer descriptors: an out-of-image tap reads at byte offset 2^31, which must lie past the end of x
-    const size_t xb = (size_t)(a.M / (a.OH * a.OW)) * a.H * a.W * a.Cin * 2;  // N images of H x W x Cin bf16
-    const size_t wb = (size_t)a.Kf * a.R * a.R * a.Cf * 2;
-    if (xb >= ((size_t)1 << 31) || wb >= ((size_t)1 << 32)) return SALUN_EINVAL;
-    a.x_bytes = (uint32_t)xb;
-    a.w_bytes = (uint32_t)wb;
-  }
-  hipLaunchKernelGGL((conv_bf16_igemm<WM, WN, BK, BTR>), dim3(mt, nt, sp.splits), dim3(64 * WM * WN), lds, st, a);
-  SALUN_LAUNCH_CHECK();
-  if (sp.splits > 1) {
+  a.stages_per_split = p.per;
+  a.part = p.splits > 1 ? static_cast<float *>(ws) : nullptr;
+  a.x_bytes = p.x_bytes;
+  a.w_bytes = p.w_bytes;
+  const int rc = launch_lds<conv_bf16_igemm<WM, WN, BK, BTR>>(dim3(p.mt, p.nt, p.splits), dim3(64 * WM * WN),
+                                                              2 * (size_t)(A_BYTES + B_BYTES), st, a);
+  if (rc != SALUN_OK) return rc;
+  if (p.splits > 1) {
     const int64_t total = (int64_t)a.M * (a.Kout / 8);
-    hipLaunchKernelGGL(k_splitk_finish, dim3(salun_grid_for(total, 256)), dim3(256), 0, st, a.part, sp.splits, a.bias, a.nbias,
+    hipLaunchKernelGGL(k_splitk_finish, dim3(salun_grid_for(total, 256)), dim3(256), 0, st, a.part, p.splits, a.bias, a.nbias,
                        a.addend, a.y, a.M, a.Kout, a.OH * a.OW);
     SALUN_LAUNCH_CHECK();
   }
   return SALUN_OK;
 }
 
+// the instantiation of the plan's tile (igemm_tile picks among these six)
 template <bool BTR>
-int dispatch_igemm(const IgArgs &a, void *ws, size_t ws_bytes, hipStream_t st) {
-  const int bk64 = (a.Cin % 64 == 0);
-  if (SALUN_BF16_TILE == 1 && bk64) return launch_igemm<2, 2, 64, BTR>(a, ws, ws_bytes, st);
-  if (SALUN_BF16_TILE == 2) return launch_igemm<2, 2, 32, BTR>(a, ws, ws_bytes, st);
-  if (SALUN_BF16_TILE == 3 && bk64) return launch_igemm<4, 1, 64, BTR>(a, ws, ws_bytes, st);
-  if (SALUN_BF16_TILE == 4) return launch_igemm<4, 1, 32, BTR>(a, ws, ws_bytes, st);
-  if (SALUN_BF16_TILE == 5) return launch_igemm<4, 2, 32, BTR>(a, ws, ws_bytes, st);
-  if (SALUN_BF16_TILE == 6) return launch_igemm<2, 4, 32, BTR>(a, ws, ws_bytes, st);
-  // 128 x 256 (eight waves) where the channel count tiles it: a third less operand traffic per MFMA, +5..13 % on the
-  // 1280-channel levels; 128 x 128 otherwise (K = 320 / 640 would pad a 256-wide tile by 37 % / 17 %)
-  if (a.Kout % 256 == 0) return launch_igemm<2, 4, 32, BTR>(a, ws, ws_bytes, st);
-  return launch_igemm<2, 2, 32, BTR>(a, ws, ws_bytes, st);
+int dispatch_igemm(const ConvDataPlan &p, const IgArgs &a, void *ws, hipStream_t st) {
+  const auto is = [&p](int wm, int wn, int bk) { return p.tile.wm == wm && p.tile.wn == wn && p.tile.bk == bk; };
+  if (is(2, 2, 64)) return launch_igemm<2, 2, 64, BTR>(p, a, ws, st);
+  if (is(2, 2, 32)) return launch_igemm<2, 2, 32, BTR>(p, a, ws, st);
+  if (is(4, 1, 64)) return launch_igemm<4, 1, 64, BTR>(p, a, ws, st);
+  if (is(4, 1, 32)) return launch_igemm<4, 1, 32, BTR>(p, a, ws, st);
+  if (is(4, 2, 32)) return launch_igemm<4, 2, 32, BTR>(p, a, ws, st);
+  return launch_igemm<2, 4, 32, BTR>(p, a, ws, st);
 }
 
 template <int R, int ST>
 int launch_wgrad(const WgArgs &a, int splits, hipStream_t st) {
   constexpr int PW = 7 * ST + R;
-  const size_t lds = 2 * (size_t)(2 * 64 * 64 + 2 * PW * PW * 64);
-  static unsigned long long attr_done = 0;  // one bit per device
-  if (salun_once_needed(&attr_done)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_bf16_wgrad<R, ST>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return SALUN_EIO;
-    salun_once_mark(&attr_done);
-  }
-  WgArgs b = a;
-  {  // buffer descriptors: an out-of-image lane reads at byte offset 2^31, which must lie past the end of both tensors
-    const size_t xb = (size_t)a.N * a.H * a.W * a.C * 2, db = (size_t)a.N * a.OH * a.OW * a.K * 2;
-    if (xb >= ((size_t)1 << 31) || db >= ((size_t)1 << 31)) return SALUN_EINVAL;
-    b.x_bytes = (uint32_t)xb;
-    b.dy_bytes = (uint32_t)db;
-  }
-  dim3 grid((a.K + 63) / 64, (a.C + 63) / 64, splits);
-  hipLaunchKernelGGL((conv_bf16_wgrad<R, ST>), grid, dim3(256), lds, st, b);
-  SALUN_LAUNCH_CHECK();
-  return SALUN_OK;
+  return launch_lds<conv_bf16_wgrad<R, ST>>(dim3((a.K + 63) / 64, (a.C + 63) / 64, splits), dim3(256),
+                                            2 * (size_t)(2 * 64 * 64 + 2 * PW * PW * 64), st, a);
 }
 
 }  // namespace
 
 // ================================================================== C-ABI =======
 SALUN_EXPORT int salun_conv2d_bf16_supported(int C, int K, int R, int stride, int pad) {
-  return supported(C, K, R, stride, pad) ? 1 : 0;
+  return conv_bf16_supported(C, K, R, stride, pad) ? 1 : 0;
 }
 
 SALUN_EXPORT int salun_conv2d_bf16_pack_weights(const float *w, uint16_t *wp, int K, int C, int R, salun_stream_t stream) {
@@ -984,97 +902,40 @@ SALUN_EXPORT int salun_bf16_pack_weights_batch(const salun_bf16_pack_job_t *jobs
 // Scratch for the reduction split of forward / backward-data: 16 fp32 copies of the larger of the two outputs is the
 // most any plan uses; a smaller (or null) workspace only disables the split.
 SALUN_EXPORT size_t salun_conv2d_bf16_data_workspace_bytes(int N, int H, int W, int C, int K, int R, int stride, int pad) {
-  if (!supported(C, K, R, stride, pad) || N < 1 || H < 1 || W < 1) return 0;
-  const int OH = (H + 2 * pad - R) / stride + 1, OW = (W + 2 * pad - R) / stride + 1;
-  const int BK = 32;
-  // tile of the variant dispatch_igemm picks (lab builds pin others)
-  const int BMt = (SALUN_BF16_TILE == 3 || SALUN_BF16_TILE == 4 || SALUN_BF16_TILE == 5) ? 256 : 128;
-  const int BNt = (SALUN_BF16_TILE == 3 || SALUN_BF16_TILE == 4) ? 64 : (SALUN_BF16_TILE == 6 ? 256 : 128);
-  const int BNf = (SALUN_BF16_TILE == 0 && K % 256 == 0) ? 256 : BNt;  // forward: output channels K
-  const int BNd = (SALUN_BF16_TILE == 0 && C % 256 == 0) ? 256 : BNt;  // backward-data: output channels C
-  size_t need = 0;
-  {  // forward
-    const int M = N * OH * OW, tiles = ((M + BMt - 1) / BMt) * ((K + BNf - 1) / BNf);
-    const SplitPlan sp = plan_split(tiles, R * R * (C / BK));
-    if (sp.splits > 1) need = (size_t)sp.splits * M * K * sizeof(float);
-  }
-  {  // backward-data
-    const int M = N * H * W, tiles = ((M + BMt - 1) / BMt) * ((C + BNd - 1) / BNd);
-    const SplitPlan sp = plan_split(tiles, R * R * (K / BK));
-    const size_t b = sp.splits > 1 ? (size_t)sp.splits * M * C * sizeof(float) : 0;
-    if (b > need) need = b;
-  }
-  return need;
+  return conv_data_ws_bytes(N, H, W, C, K, R, stride, pad);
 }
-
-extern "C" int salun_conv2d_bf16_forward_ring(const uint16_t *x, const uint16_t *wp, const float *bias, const float *nbias,
-                                              const uint16_t *addend, uint16_t *y, int N, int H, int W, int C, int K, int R,
-                                              int stride, int pad, hipStream_t st);
 
 SALUN_EXPORT int salun_conv2d_bf16_forward(const uint16_t *x, const uint16_t *wp, const float *bias, const float *nbias,
                                            const uint16_t *addend, uint16_t *y, int N, int H, int W, int C, int K, int R,
                                            int stride, int pad, void *ws, size_t ws_bytes, salun_stream_t stream) {
-  if (!x || !wp || !y || N < 1 || H < 1 || W < 1 || !supported(C, K, R, stride, pad)) return SALUN_EINVAL;
-  if (!salun_aligned16(x) || !salun_aligned16(wp)) return SALUN_EINVAL;
-  const int OH = (H + 2 * pad - R) / stride + 1, OW = (W + 2 * pad - R) / stride + 1;
-  if (OH < 1 || OW < 1 || (int64_t)N * H * W * C >= (int64_t(1) << 31) || (int64_t)N * OH * OW * K >= (int64_t(1) << 31))
-    return SALUN_EINVAL;
-  // the staging addresses use 24-bit multiplies: pixel counts and channel counts below 2^24
-  if ((int64_t)N * H * W >= (1 << 24) || (int64_t)N * OH * OW >= (1 << 24) || C >= (1 << 24) || K >= (1 << 24)) return SALUN_EINVAL;
-  {  // the LDS-DMA ring form (salun_gemm.hip) where the launch has enough tiles to do without a reduction split
-    const int rc = salun_conv2d_bf16_forward_ring(x, wp, bias, nbias, addend, y, N, H, W, C, K, R, stride, pad,
-                                                  salun_hip_stream(stream));
-    if (rc != 0) return rc < 0 ? rc : SALUN_OK;
-  }
-  IgArgs a{x, wp, bias, nbias, addend, y, N * OH * OW, H, W, C, OH, OW, K, R, stride, pad, 1, K, C, nullptr, 0, 0u, 0u};
-  return dispatch_igemm<false>(a, ws, ws_bytes, salun_hip_stream(stream));
+  if (!x || !wp || !y || !salun_aligned16(x) || !salun_aligned16(wp)) return SALUN_EINVAL;
+  const bool epi_al16 = salun_aligned16(bias) && salun_aligned16(nbias) && salun_aligned16(addend) && salun_aligned16(y);
+  const ConvDataPlan p = plan_conv_data(false, N, H, W, C, K, R, stride, pad, epi_al16, ws != nullptr, ws_bytes, bf16_switches());
+  if (p.rc != SALUN_OK) return p.rc;
+  hipStream_t st = salun_hip_stream(stream);
+  if (p.ring.wgm)
+    return salun_conv_bf16_ring_launch(p.ring.wgm, p.ring.wgn, p.ring.nst, x, wp, bias, nbias, addend, y, (int)p.M, H, W, C,
+                                       p.OH, p.OW, K, R, stride, pad, st);
+  IgArgs a{x, wp, bias, nbias, addend, y, (int)p.M, H, W, C, p.OH, p.OW, K, R, stride, pad, 1, K, C, nullptr, 0, 0u, 0u};
+  return dispatch_igemm<false>(p, a, ws, st);
 }
 
 // dx[N][H][W][C] from dy[N][OH][OW][K]; `addend` (same shape as dx, may be null) rides in the epilogue.
 SALUN_EXPORT int salun_conv2d_bf16_backward_data(const uint16_t *dy, const uint16_t *wp, const uint16_t *addend,
                                                  uint16_t *dx, int N, int H, int W, int C, int K, int R, int stride,
                                                  int pad, void *ws, size_t ws_bytes, salun_stream_t stream) {
-  if (!dy || !wp || !dx || N < 1 || H < 1 || W < 1 || !supported(C, K, R, stride, pad)) return SALUN_EINVAL;
-  if (!salun_aligned16(dy) || !salun_aligned16(wp)) return SALUN_EINVAL;
-  const int OH = (H + 2 * pad - R) / stride + 1, OW = (W + 2 * pad - R) / stride + 1;
-  if (OH < 1 || OW < 1 || (int64_t)N * H * W * C >= (int64_t(1) << 31) || (int64_t)N * OH * OW * K >= (int64_t(1) << 31))
-    return SALUN_EINVAL;
-  // the staging addresses use 24-bit multiplies: pixel counts and channel counts below 2^24
-  if ((int64_t)N * H * W >= (1 << 24) || (int64_t)N * OH * OW >= (1 << 24) || C >= (1 << 24) || K >= (1 << 24)) return SALUN_EINVAL;
+  if (!dy || !wp || !dx || !salun_aligned16(dy) || !salun_aligned16(wp)) return SALUN_EINVAL;
+  const ConvDataPlan p = plan_conv_data(true, N, H, W, C, K, R, stride, pad, true, ws != nullptr, ws_bytes, bf16_switches());
+  if (p.rc != SALUN_OK) return p.rc;
   // walk dX's pixels; the source is dY (zero-upsampled by `stride`), padding R-1-pad, taps flipped in the weight read
-  IgArgs a{dy, wp, nullptr, nullptr, addend, dx, N * H * W, OH, OW, K, H, W, C, R, 1, R - 1 - pad, stride, K, C, nullptr, 0, 0u, 0u};
-  return dispatch_igemm<true>(a, ws, ws_bytes, salun_hip_stream(stream));
-}
-
-// 1x1 stride-1 unpadded convolutions (and the Linear layers, which arrive as such) are plain dY^T . X products: K16's
-// TN kernel (salun_gemm.hip) takes them.  SALUN_WGRAD_TN=0 keeps them on the tap kernel below (A/B measurements).
-extern "C" int salun_gemm_bf16_tn_supported(int64_t M, int Na, int Nb);
-extern "C" size_t salun_gemm_bf16_tn_workspace_bytes(int64_t M, int Na, int Nb, int variant);
-extern "C" int salun_gemm_bf16_tn(const void *dy, const void *x, float *dw, int64_t M, int Na, int Nb, int accumulate, int variant,
-                                  void *ws, size_t ws_bytes, salun_stream_t stream);
-static bool tn_route(int64_t M, int C, int K, int R, int stride, int pad) {
-  static const int on = [] { const char *e = getenv("SALUN_WGRAD_TN"); return e ? atoi(e) : 1; }();
-  // short reductions (the 8 x 8 level: M = 512) keep the tap kernel: with one split it adds straight into the gradient,
-  // the GEMM would need partials there (profiles/r04_gemmbench_bf16.txt: 11.6 vs 17.5 us, 51 vs 61 us)
-  return on && R == 1 && stride == 1 && pad == 0 && M >= 1024 && salun_gemm_bf16_tn_supported(M, K, C);
+  IgArgs a{dy, wp, nullptr, nullptr, addend, dx, (int)p.M, p.OH, p.OW, K, H, W, C, R, 1, R - 1 - pad, stride, K, C, nullptr, 0, 0u, 0u};
+  return dispatch_igemm<true>(p, a, ws, salun_hip_stream(stream));
 }
 
 SALUN_EXPORT size_t salun_conv2d_bf16_wgrad_workspace_bytes(int N, int H, int W, int C, int K, int R, int stride, int pad) {
-  if (!supported(C, K, R, stride, pad) || N < 1) return 0;
-  const int OH = (H + 2 * pad - R) / stride + 1, OW = (W + 2 * pad - R) / stride + 1;
-  const int chunks = N * ((OH + 7) / 8) * ((OW + 7) / 8);
-  const int tiles = ((K + 63) / 64) * ((C + 63) / 64);
-  const size_t tap = (size_t)wgrad_splits(tiles, chunks) * R * R * K * C * sizeof(float) + (size_t)COLSUM_CHUNKS * K * sizeof(float);
-  if (tn_route((int64_t)N * H * W, C, K, R, stride, pad)) {
-    // never 0 ("unsupported"): the column-sum partials of the bias gradient follow the GEMM's partials.  The larger
-    // of the two routes: a gradient pointer that is not 16-byte aligned (an odd-sized parameter ahead of it in the
-    // flat arena) takes the tap kernels at launch time, and this query does not see the pointer.
-    size_t b = salun_gemm_bf16_tn_workspace_bytes((int64_t)N * H * W, K, C, 0);
-    b = (b + 255) & ~(size_t)255;
-    b += (size_t)COLSUM_CHUNKS * K * sizeof(float);
-    return b > tap ? b : tap;
-  }
-  return tap;
+  // never 0 for a supported shape: the column-sum partials of the bias gradient follow the weight partials.  The larger
+  // of the two routes: this query does not see the gradient pointer whose alignment admits the TN GEMM.
+  return plan_conv_wgrad(N, H, W, C, K, R, stride, pad, true, SIZE_MAX, bf16_switches()).need;
 }
 
 // dw fp32 OIHW [K][C][R][R] (+= when accumulate); db fp32 [K] or null (the bias gradient, += when accumulate); dnb fp32
@@ -1082,49 +943,37 @@ SALUN_EXPORT size_t salun_conv2d_bf16_wgrad_workspace_bytes(int N, int H, int W,
 SALUN_EXPORT int salun_conv2d_bf16_backward_weight_ex(const uint16_t *x, const uint16_t *dy, float *dw, float *db, float *dnb,
                                                       int N, int H, int W, int C, int K, int R, int stride, int pad,
                                                       int accumulate, void *ws, size_t ws_bytes, salun_stream_t stream) {
-  if (!x || !dy || !dw || !ws || N < 1 || !supported(C, K, R, stride, pad)) return SALUN_EINVAL;
-  if (!salun_aligned16(x) || !salun_aligned16(dy)) return SALUN_EINVAL;
+  if (!x || !dy || !dw || !ws || !salun_aligned16(x) || !salun_aligned16(dy)) return SALUN_EINVAL;
   if (dnb && N > COLSUM_CHUNKS) return SALUN_EINVAL;
-  const size_t need = salun_conv2d_bf16_wgrad_workspace_bytes(N, H, W, C, K, R, stride, pad);
-  if (ws_bytes < need) return SALUN_ENOSPC;
-  const int OH = (H + 2 * pad - R) / stride + 1, OW = (W + 2 * pad - R) / stride + 1;
-  if (tn_route((int64_t)N * H * W, C, K, R, stride, pad) && salun_aligned16(dw)) {  // else: the tap kernels take any dw
-    const int64_t M = (int64_t)N * H * W;
-    size_t gb = salun_gemm_bf16_tn_workspace_bytes(M, K, C, 0);
-    const int rc = salun_gemm_bf16_tn(dy, x, dw, M, K, C, accumulate, 0, ws, gb, stream);
-    if (rc != SALUN_OK) return rc;
-    if (db || dnb) {
-      gb = (gb + 255) & ~(size_t)255;
-      float *cpart = reinterpret_cast<float *>(static_cast<char *>(ws) + gb);
-      return launch_colsum(dy, cpart, db, dnb, M, K, N, accumulate, salun_hip_stream(stream));
-    }
-    return SALUN_OK;
-  }
-  WgArgs a;
-  a.x = x; a.dy = dy; a.part = static_cast<float *>(ws);
-  a.N = N; a.H = H; a.W = W; a.C = C; a.OH = OH; a.OW = OW; a.K = K; a.pad = pad;
-  a.tiles_h = (OH + 7) / 8; a.tiles_w = (OW + 7) / 8;
-  a.chunks = N * a.tiles_h * a.tiles_w;
-  const int tiles = ((K + 63) / 64) * ((C + 63) / 64);
-  const int splits = wgrad_splits(tiles, a.chunks);
-  a.per_split = (a.chunks + splits - 1) / splits;
-  a.dw = dw; a.direct = splits == 1; a.accumulate = accumulate;
+  const WgradPlan p = plan_conv_wgrad(N, H, W, C, K, R, stride, pad, salun_aligned16(dw), ws_bytes, bf16_switches());
+  if (p.rc != SALUN_OK) return p.rc;
   hipStream_t st = salun_hip_stream(stream);
-  int rc;
-  if (R == 3 && stride == 1) rc = launch_wgrad<3, 1>(a, splits, st);
-  else if (R == 3) rc = launch_wgrad<3, 2>(a, splits, st);
-  else if (stride == 1) rc = launch_wgrad<1, 1>(a, splits, st);
-  else rc = launch_wgrad<1, 2>(a, splits, st);
-  if (rc != SALUN_OK) return rc;
-  if (!a.direct) {
-    const int64_t kc = (int64_t)K * C;
-    hipLaunchKernelGGL(k_wgrad_reduce_bf16, dim3((unsigned)((kc + 63) / 64)), dim3(256), 0, st, a.part, dw, K, C, R * R,
-                       splits, accumulate);
-    SALUN_LAUNCH_CHECK();
+  if (p.tn) {
+    const int rc = salun_gemm_bf16_tn(dy, x, dw, p.M, K, C, accumulate, 0, ws, p.tnp.ws_bytes(K, C), stream);
+    if (rc != SALUN_OK) return rc;
+  } else {
+    WgArgs a;
+    a.x = x; a.dy = dy; a.part = static_cast<float *>(ws);
+    a.N = N; a.H = H; a.W = W; a.C = C; a.OH = p.OH; a.OW = p.OW; a.K = K; a.pad = pad;
+    a.tiles_h = p.tiles_h; a.tiles_w = p.tiles_w; a.chunks = p.chunks; a.per_split = p.per_split;
+    a.dw = dw; a.direct = p.direct; a.accumulate = accumulate;
+    a.x_bytes = p.x_bytes; a.dy_bytes = p.dy_bytes;
+    int rc;
+    if (R == 3 && stride == 1) rc = launch_wgrad<3, 1>(a, p.splits, st);
+    else if (R == 3) rc = launch_wgrad<3, 2>(a, p.splits, st);
+    else if (stride == 1) rc = launch_wgrad<1, 1>(a, p.splits, st);
+    else rc = launch_wgrad<1, 2>(a, p.splits, st);
+    if (rc != SALUN_OK) return rc;
+    if (!p.direct) {
+      const int64_t kc = (int64_t)K * C;
+      hipLaunchKernelGGL(k_wgrad_reduce_bf16, dim3((unsigned)((kc + 63) / 64)), dim3(256), 0, st, a.part, dw, K, C, R * R,
+                         p.splits, accumulate);
+      SALUN_LAUNCH_CHECK();
+    }
   }
   if (db || dnb) {
-    float *cpart = a.part + (size_t)splits * R * R * K * C;
-    return launch_colsum(dy, cpart, db, dnb, (int64_t)N * OH * OW, K, N, accumulate, st);
+    float *cpart = reinterpret_cast<float *>(static_cast<char *>(ws) + p.lay.colsum_off);
+    return launch_colsum(dy, cpart, db, dnb, (int64_t)N * p.OH * p.OW, K, N, accumulate, st);
   }
   return SALUN_OK;
 }
@@ -1143,4 +992,26 @@ SALUN_EXPORT int salun_conv2d_bf16_backward_weight(const uint16_t *x, const uint
                                                    void *ws, size_t ws_bytes, salun_stream_t stream) {
   return salun_conv2d_bf16_backward_weight_ex(x, dy, dw, db, nullptr, N, H, W, C, K, R, stride, pad, accumulate, ws, ws_bytes,
                                               stream);
+}
+
+SALUN_EXPORT int salun_conv2d_bf16_route(int direction, int N, int H, int W, int C, int K, int R, int stride, int pad,
+                                         unsigned flags, size_t ws_bytes, char *buf, size_t buflen, int *nsplit) {
+  if (!buf || buflen < 1) return SALUN_EINVAL;
+  buf[0] = 0;
+  if (nsplit) *nsplit = 0;
+  const bool out_al16 = !(flags & SALUN_ROUTE_OUT_UNALIGNED);
+  const Bf16Switches sw = route_switches(flags);
+  int rc = SALUN_EINVAL, len = 0, ns = 0;
+  if (direction == SALUN_ROUTE_FORWARD || direction == SALUN_ROUTE_BACKWARD_DATA) {
+    const bool dgrad = direction == SALUN_ROUTE_BACKWARD_DATA;
+    const ConvDataPlan p = plan_conv_data(dgrad, N, H, W, C, K, R, stride, pad, out_al16, ws_bytes > 0, ws_bytes, sw);
+    if ((rc = p.rc) == SALUN_OK) { len = conv_data_label(buf, buflen, p, dgrad); ns = p.ring.wgm ? 1 : p.splits; }
+  } else if (direction == SALUN_ROUTE_BACKWARD_WEIGHT) {
+    const WgradPlan p = plan_conv_wgrad(N, H, W, C, K, R, stride, pad, out_al16, ws_bytes, sw);
+    if ((rc = p.rc) == SALUN_OK) { len = conv_wgrad_label(buf, buflen, p, R, stride); ns = p.tn ? p.tnp.splits : p.splits; }
+  }
+  if (rc != SALUN_OK) return rc;
+  if (len < 0 || (size_t)len >= buflen) { buf[0] = 0; return SALUN_ENOSPC; }
+  if (nsplit) *nsplit = ns;
+  return SALUN_OK;
 }

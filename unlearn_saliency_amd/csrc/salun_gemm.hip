@@ -23,9 +23,8 @@
 // dimension and the alignment allow (mode chosen per segment on the host), scalar otherwise.  Under-filled launches
 // split the reduction over blockIdx.z into fp32 partial images that a second kernel folds in a fixed order (no float
 // atomics anywhere: results are deterministic).
-#include "salun_common.h"
+#include "salun_bf16_internal.h"
 #include <type_traits>
-#include <cstdlib>
 
 namespace {
 
@@ -1102,24 +1101,6 @@ __global__ __launch_bounds__(64 * WGM * WGN, (BK == 32 && WGM * WGN == 8) ? 4 : 
   }
 }
 
-template <int WGM, int WGN, int NST, int BK = 64>
-int launch_gemm_bf16_r(const GbArgs &g0, hipStream_t st) {
-  GbArgs g = g0;
-  constexpr int BMt = 64 * WGM, BNt = 64 * WGN;
-  g.tiles_m = (g.M + BMt - 1) / BMt;
-  g.tiles_n = g.N / BNt;
-  const size_t ldsb = (size_t)NST * (BMt + BNt) * BK * 2;
-  static unsigned long long configured = 0;  // one bit per device: the opt-in is per device, not per process
-  if (salun_once_needed(&configured)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_bf16_nt_r<WGM, WGN, NST, BK>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb);
-    salun_once_mark(&configured);
-  }
-  hipLaunchKernelGGL((k_gemm_bf16_nt_r<WGM, WGN, NST, BK>), dim3(g.tiles_m * g.tiles_n), dim3(64 * WGM * WGN), ldsb, st, g);
-  SALUN_LAUNCH_CHECK();
-  return SALUN_OK;
-}
-
 // ------------------------------------------------------------------------------------------- K16 ring as a convolution
 // The same ring with the A rows GATHERED: row m of the implicit GEMM is output pixel m, and for reduction stage
 // (tap (r, s), 32 input channels from c0) its 64 bytes are x[n][oh*stride - pad + r][ow*stride - pad + s][c0 .. c0+31] of
@@ -1344,24 +1325,6 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN == 8) ? 4 : 1) void k_co
   }
 }
 
-template <int WGM, int WGN, int NST>
-int launch_conv_ring(const IrArgs &g0, hipStream_t st) {
-  IrArgs g = g0;
-  constexpr int BMt = 64 * WGM, BNt = 64 * WGN;
-  g.tiles_m = (g.M + BMt - 1) / BMt;
-  g.tiles_n = g.Kout / BNt;
-  const size_t ldsb = (size_t)NST * (BMt + BNt) * 64;
-  static unsigned long long configured = 0;  // one bit per device: the opt-in is per device, not per process
-  if (salun_once_needed(&configured)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_conv_bf16_ring<WGM, WGN, NST>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb);
-    salun_once_mark(&configured);
-  }
-  hipLaunchKernelGGL((k_conv_bf16_ring<WGM, WGN, NST>), dim3(g.tiles_m * g.tiles_n), dim3(64 * WGM * WGN), ldsb, st, g);
-  SALUN_LAUNCH_CHECK();
-  return SALUN_OK;
-}
-
 // ------------------------------------------------------------------------------------------------ K16 TN (weight gradients)
 // dW[Na][Nb] (fp32) (+)= sum_m dY[m][Na] . X[m][Nb]: the reduction index is the SLOW axis of both operands, so the 16-byte
 // pieces the DMA drops into LDS hold 8 features of ONE token and an MFMA operand (8 tokens of one feature) is gathered by
@@ -1583,46 +1546,6 @@ __global__ __launch_bounds__(256) void k_tn_reduce(const float *__restrict__ par
   }
 }
 
-#ifndef SALUN_TN_TARGET
-#define SALUN_TN_TARGET 256  // workgroups a launch is split up to: 512 until backward-weight moved to the side stream (profiles/r06_sd_split_targets.txt)
-#endif
-struct TnPlan { int variant, ta, tb, rst, tiles_a, tiles_b, stages, splits, per_split; };
-
-// variant 1: 128 x 128, 64-token stages x 3 (96 KB, one workgroup per CU); 2: 128 x 128, 32-token stages x 4 (64 KB, two
-// per CU); 3: 256 x 128, 8 waves, 64-token stages x 3 (144 KB)
-TnPlan tn_plan(int64_t M, int Na, int Nb, int variant) {
-  TnPlan p;
-  if (variant == 0) variant = 2;
-  p.variant = variant;
-  p.ta = variant == 3 ? 256 : 128; p.tb = 128;
-  p.rst = variant == 2 ? 32 : 64;
-  p.tiles_a = (Na + p.ta - 1) / p.ta; p.tiles_b = (Nb + p.tb - 1) / p.tb;
-  p.stages = (int)((M + p.rst - 1) / p.rst);
-  const int tiles = p.tiles_a * p.tiles_b;
-  const int min_stages = 256 / p.rst;           // a split reduces over >= 256 tokens
-  int splits = (SALUN_TN_TARGET + tiles - 1) / tiles;
-  if (splits > p.stages / min_stages) splits = p.stages / min_stages;
-  if (splits > 64) splits = 64;
-  if (splits < 1) splits = 1;
-  p.per_split = (p.stages + splits - 1) / splits;
-  p.splits = (p.stages + p.per_split - 1) / p.per_split;
-  return p;
-}
-
-template <int WGA, int WGB, int RST, int NST>
-int launch_gemm_bf16_tn(const TnArgs &g, int splits, hipStream_t st) {
-  const size_t ldsb = (size_t)NST * (64 * WGA + 64 * WGB) / 32 * RST * 64;
-  static unsigned long long configured = 0;  // one bit per device: the opt-in is per device, not per process
-  if (salun_once_needed(&configured)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_bf16_tn<WGA, WGB, RST, NST>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb);
-    salun_once_mark(&configured);
-  }
-  hipLaunchKernelGGL((k_gemm_bf16_tn<WGA, WGB, RST, NST>), dim3(g.tiles_a * g.tiles_b * splits), dim3(64 * WGA * WGB), ldsb, st, g);
-  SALUN_LAUNCH_CHECK();
-  return SALUN_OK;
-}
-
 // fp32 [N][K] -> bf16 [K][N] (the weight image the input-gradient GEMM reads); 32 x 32 tiles through LDS
 __global__ __launch_bounds__(256) void k_pack_bf16_t(const float *__restrict__ w, uint16_t *__restrict__ wt, int N, int K) {
   __shared__ float tile[32][33];
@@ -1651,143 +1574,92 @@ __global__ __launch_bounds__(256) void k_pack_bf16(const float *__restrict__ w, 
   }
 }
 
-template <int WGM, int WGN, bool DB>
-int launch_gemm_bf16(const GbArgs &g0, hipStream_t st) {
-  GbArgs g = g0;
-  constexpr int BMt = 64 * WGM, BNt = 64 * WGN;
-  g.tiles_m = (g.M + BMt - 1) / BMt;
-  g.tiles_n = g.N / BNt;
-  const size_t ldsb = (size_t)(DB ? 2 : 1) * (BMt + BNt) * 128;
-  static unsigned long long configured = 0;  // one bit per device: the opt-in is per device, not per process
-  if (salun_once_needed(&configured)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_bf16_nt<WGM, WGN, DB>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb);
-    salun_once_mark(&configured);
-  }
-  hipLaunchKernelGGL((k_gemm_bf16_nt<WGM, WGN, DB>), dim3(g.tiles_m * g.tiles_n), dim3(64 * WGM * WGN), ldsb, st, g);
-  SALUN_LAUNCH_CHECK();
-  return SALUN_OK;
+// variant V of NT_ROWS: the row names the kernel instantiation, the plan its grid
+template <int V>
+int launch_gemm_nt(const NtPlan &p, GbArgs g, hipStream_t st) {
+  constexpr NtRow r = NT_ROWS[V];
+  g.tiles_m = p.tiles_m;
+  g.tiles_n = p.tiles_n;
+  const dim3 grid(p.grid), block(64 * r.wgm * r.wgn);
+  if constexpr (r.family == NT_PLAIN) return launch_lds<k_gemm_bf16_nt<r.wgm, r.wgn, r.nst == 2>>(grid, block, r.lds(), st, g);
+  else if constexpr (r.family == NT_PERSISTENT)
+    return launch_lds<k_gemm_bf16_nt_p<r.wgm, r.wgn>>(grid, block, r.lds(), st, g, p.tiles_per_wg);
+  else return launch_lds<k_gemm_bf16_nt_r<r.wgm, r.wgn, r.nst, r.bk>>(grid, block, r.lds(), st, g);
 }
 
-template <int WGM, int WGN>
-int launch_gemm_bf16_p(const GbArgs &g0, hipStream_t st) {
-  GbArgs g = g0;
+template <int WGM, int WGN, int NST>
+int launch_conv_ring(IrArgs g, hipStream_t st) {
   constexpr int BMt = 64 * WGM, BNt = 64 * WGN;
   g.tiles_m = (g.M + BMt - 1) / BMt;
-  g.tiles_n = g.N / BNt;
-  const size_t ldsb = (size_t)2 * (BMt + BNt) * 128;
-  static unsigned long long configured = 0;  // one bit per device: the opt-in is per device, not per process
-  if (salun_once_needed(&configured)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_bf16_nt_p<WGM, WGN>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb);
-    salun_once_mark(&configured);
-  }
-  const int ntile = g.tiles_m * g.tiles_n;
-  // 2 workgroups per CU (LDS: 2 x 64-80 KB); each walks a run of tiles inside its XCD's contiguous range
-  const int per_xcd = (ntile + 7) / 8;
-  int runs = 64;                                   // workgroups per XCD
-  if (runs > per_xcd) runs = per_xcd;
-  const int tiles_per_wg = (per_xcd + runs - 1) / runs;
-  runs = (per_xcd + tiles_per_wg - 1) / tiles_per_wg;
-  hipLaunchKernelGGL((k_gemm_bf16_nt_p<WGM, WGN>), dim3(runs * 8), dim3(64 * WGM * WGN), ldsb, st, g, tiles_per_wg);
-  SALUN_LAUNCH_CHECK();
-  return SALUN_OK;
+  g.tiles_n = g.Kout / BNt;
+  return launch_lds<k_conv_bf16_ring<WGM, WGN, NST>>(dim3(g.tiles_m * g.tiles_n), dim3(64 * WGM * WGN),
+                                                     (size_t)NST * (BMt + BNt) * 64, st, g);
+}
+
+template <int WGA, int WGB, int RST, int NST>
+int launch_gemm_bf16_tn(const TnArgs &g, int splits, hipStream_t st) {
+  return launch_lds<k_gemm_bf16_tn<WGA, WGB, RST, NST>>(dim3(g.tiles_a * g.tiles_b * splits), dim3(64 * WGA * WGB),
+                                                        (size_t)NST * (64 * WGA + 64 * WGB) / 32 * RST * 64, st, g);
 }
 
 }  // namespace
 
-// Internal (not exported): salun_conv2d_bf16_forward (salun_conv_bf16.hip) tries this first.  Returns 1 when the ring
-// kernel took the convolution, 0 when the shape is left to the register-staged kernel (few tiles: that one can split the
-// reduction; channel counts that do not tile), a negative error otherwise.
-extern "C" int salun_conv2d_bf16_forward_ring(const uint16_t *x, const uint16_t *wp, const float *bias, const float *nbias,
-                                              const uint16_t *addend, uint16_t *y, int N, int H, int W, int C, int K, int R,
-                                              int stride, int pad, hipStream_t st) {
-  static const int on = [] { const char *e = getenv("SALUN_CONV_RING"); return e ? atoi(e) : 1; }();
-  const int OH = (H + 2 * pad - R) / stride + 1, OW = (W + 2 * pad - R) / stride + 1;
-  const int64_t M = (int64_t)N * OH * OW;
-  if (!on || C % 32 != 0 || K % 64 != 0 || (R != 1 && R != 3) || M >= (1 << 30)) return 0;
-  // Measured on the SD layer table (tools/convbench_bf16.py, round 4): the ring wins the 1 x 1 convolutions (299 vs 229 and
-  // 282 vs 188 TFLOP/s) and LOSES the 3 x 3 ones (442 vs 540 TFLOP/s over the table: 90 .. 720 stages of 8 MFMAs per wave,
-  // gathered 64-byte rows through the LDS-DMA path, which the register-staged kernel with its 128 x 256 tiles out-runs).
-  // on == 3 forces it for every eligible shape (tests, A/B).
-  if (R != 1 && on != 3 && on != 2) return 0;
-  if ((bias && !salun_aligned16(bias)) || (nbias && !salun_aligned16(nbias)) || (addend && !salun_aligned16(addend)) ||
-      !salun_aligned16(y))
-    return 0;
-  IrArgs g{x, wp, bias, nbias, addend, y, (int)M, H, W, C, OH, OW, K, R, stride, pad, 0, 0};
-  const int64_t t256 = (M + 255) / 256;
-  if (on == 2 && K % 128 == 0) return launch_conv_ring<2, 2, 4>(g, st) == SALUN_OK ? 1 : SALUN_EIO;   // A/B: pin the 128 x 128 form
-  if (K % 128 == 0 && t256 * (K / 128) >= 128) return launch_conv_ring<4, 2, 3>(g, st) == SALUN_OK ? 1 : SALUN_EIO;
-  if (K % 128 != 0 && t256 * (K / 64) >= 128) return launch_conv_ring<4, 1, 3>(g, st) == SALUN_OK ? 1 : SALUN_EIO;
-  if (K % 128 == 0 && ((M + 127) / 128) * (K / 128) >= 128) return launch_conv_ring<2, 2, 4>(g, st) == SALUN_OK ? 1 : SALUN_EIO;
-  return 0;
+int salun_conv_bf16_ring_launch(int wgm, int wgn, int nst, const uint16_t *x, const uint16_t *wp, const float *bias,
+                                const float *nbias, const uint16_t *addend, uint16_t *y, int M, int H, int W, int C, int OH,
+                                int OW, int K, int R, int stride, int pad, hipStream_t st) {
+  const IrArgs g{x, wp, bias, nbias, addend, y, M, H, W, C, OH, OW, K, R, stride, pad, 0, 0};
+  if (wgm == 2 && wgn == 2 && nst == 4) return launch_conv_ring<2, 2, 4>(g, st);
+  if (wgm == 4 && wgn == 2 && nst == 3) return launch_conv_ring<4, 2, 3>(g, st);
+  if (wgm == 4 && wgn == 1 && nst == 3) return launch_conv_ring<4, 1, 3>(g, st);
+  return SALUN_EINVAL;
 }
 
-SALUN_EXPORT int salun_gemm_bf16_supported(int64_t M, int N, int K) {
-  return (M >= 1 && N >= 64 && K >= 64 && N % 64 == 0 && K % 64 == 0 && M * (int64_t)K < (1ll << 31) &&
-          (int64_t)N * K < (1ll << 31)) ? 1 : 0;
-}
+SALUN_EXPORT int salun_gemm_bf16_supported(int64_t M, int N, int K) { return gemm_bf16_nt_supported(M, N, K) ? 1 : 0; }
 
-// variant: 0 = choose; 1 = 128 tokens x 128 features double-buffered, 2 = same single-buffered, 3 = 256 tokens x 64
-// features double-buffered, 4 = same single-buffered, 5 / 6 = the persistent forms of 1 / 3 (A/B measurements:
-// tools/gemmbench_bf16.py)
+// variant: 0 = choose (nt_choose), 1..13 = pin a row of NT_ROWS (salun_bf16_plan.h; A/B measurements: tools/gemmbench_bf16.py)
 SALUN_EXPORT int salun_gemm_bf16_nt(const void *x, const void *w, const float *bias, const void *addend, void *y, int64_t M,
                                     int N, int K, int variant, salun_stream_t stream) {
-  if (!salun_gemm_bf16_supported(M, N, K) || !x || !w || !y) return SALUN_EINVAL;
-  if (!salun_aligned16(x) || !salun_aligned16(w) || !salun_aligned16(y) || (bias && !salun_aligned16(bias)) ||
-      (addend && !salun_aligned16(addend)))
+  if (!x || !w || !y) return SALUN_EINVAL;
+  if (!salun_aligned16(x) || !salun_aligned16(w) || !salun_aligned16(y) || !salun_aligned16(bias) || !salun_aligned16(addend))
     return SALUN_EINVAL;
+  const NtPlan p = plan_gemm_nt(M, N, K, variant);
+  if (p.rc != SALUN_OK) return p.rc;
   GbArgs g;
   g.x = static_cast<const uint16_t *>(x); g.w = static_cast<const uint16_t *>(w); g.bias = bias;
   g.addend = static_cast<const uint16_t *>(addend); g.y = static_cast<uint16_t *>(y);
   g.M = (int)M; g.N = N; g.K = K; g.tiles_m = g.tiles_n = 0;
   hipStream_t st = salun_hip_stream(stream);
-  if (variant == 0) {
-    // measured on the SD shapes (profiles/r04_gemmbench_bf16.txt): the 8-wave 256 x 128 ring with 32-deep stages (two
-    // workgroups per CU) wins wherever it has >= ~128 tiles; the 4-wave 128 x 128 ring on smaller problems; feature counts
-    // that are multiples of 64 only: 256 x 64, 32-deep
-    if (N % 128 != 0) variant = 13;
-    else variant = (((M + 255) / 256) * (int64_t)(N / 128) >= 128) ? 11 : 10;
-  }
-  if ((variant == 1 || variant == 2) && N % 128 != 0) return SALUN_EINVAL;
-  switch (variant) {
-    case 1: return launch_gemm_bf16<2, 2, true>(g, st);
-    case 2: return launch_gemm_bf16<2, 2, false>(g, st);
-    case 3: return launch_gemm_bf16<4, 1, true>(g, st);
-    case 4: return launch_gemm_bf16<4, 1, false>(g, st);
-    case 5: return (N % 128 == 0) ? launch_gemm_bf16_p<2, 2>(g, st) : SALUN_EINVAL;
-    case 6: return launch_gemm_bf16_p<4, 1>(g, st);
-    case 7: return (N % 128 == 0) ? launch_gemm_bf16_r<2, 2, 4>(g, st) : SALUN_EINVAL;   // 128 x 128, 4 stages (128 KB)
-    case 8: return (N % 128 == 0) ? launch_gemm_bf16_r<4, 2, 3>(g, st) : SALUN_EINVAL;   // 256 x 128, 8 waves, 3 stages (144 KB)
-    case 9: return launch_gemm_bf16_r<4, 1, 3>(g, st);                                   // 256 x 64, 3 stages (120 KB)
-    case 10: return (N % 128 == 0) ? launch_gemm_bf16_r<2, 2, 3>(g, st) : SALUN_EINVAL;  // 128 x 128, 3 stages (96 KB)
-    case 11: return (N % 128 == 0) ? launch_gemm_bf16_r<4, 2, 3, 32>(g, st) : SALUN_EINVAL;  // 256 x 128, 32-deep stages (72 KB: two per CU)
-    case 12: return (N % 128 == 0) ? launch_gemm_bf16_r<2, 2, 4, 32>(g, st) : SALUN_EINVAL;  // 128 x 128, 32-deep x 4 (64 KB: two per CU)
-    case 13: return launch_gemm_bf16_r<4, 1, 3, 32>(g, st);                                  // 256 x 64, 32-deep (60 KB: two per CU)
-    default: return SALUN_EINVAL;
+  switch (p.variant) {
+    case 1: return launch_gemm_nt<1>(p, g, st);
+    case 2: return launch_gemm_nt<2>(p, g, st);
+    case 3: return launch_gemm_nt<3>(p, g, st);
+    case 4: return launch_gemm_nt<4>(p, g, st);
+    case 5: return launch_gemm_nt<5>(p, g, st);
+    case 6: return launch_gemm_nt<6>(p, g, st);
+    case 7: return launch_gemm_nt<7>(p, g, st);
+    case 8: return launch_gemm_nt<8>(p, g, st);
+    case 9: return launch_gemm_nt<9>(p, g, st);
+    case 10: return launch_gemm_nt<10>(p, g, st);
+    case 11: return launch_gemm_nt<11>(p, g, st);
+    case 12: return launch_gemm_nt<12>(p, g, st);
+    default: return launch_gemm_nt<13>(p, g, st);
   }
 }
 
 // dW fp32 [Na][Nb] (+= when accumulate) = dY^T . X over M tokens; dY bf16 [M][Na], X bf16 [M][Nb].  Na, Nb multiples of
 // 32.  `ws` holds the split partials (salun_gemm_bf16_tn_workspace_bytes; may be null when that is 0).
-SALUN_EXPORT int salun_gemm_bf16_tn_supported(int64_t M, int Na, int Nb) {
-  return M >= 1 && M < (int64_t(1) << 24) && Na >= 32 && Nb >= 32 && Na % 32 == 0 && Nb % 32 == 0 &&
-         (int64_t)M * Na < (int64_t(1) << 31) && (int64_t)M * Nb < (int64_t(1) << 31);
-}
+SALUN_EXPORT int salun_gemm_bf16_tn_supported(int64_t M, int Na, int Nb) { return gemm_bf16_tn_supported(M, Na, Nb) ? 1 : 0; }
 
 SALUN_EXPORT size_t salun_gemm_bf16_tn_workspace_bytes(int64_t M, int Na, int Nb, int variant) {
-  if (!salun_gemm_bf16_tn_supported(M, Na, Nb)) return 0;
-  const TnPlan p = tn_plan(M, Na, Nb, variant);
-  return p.splits > 1 ? (size_t)p.splits * Na * Nb * sizeof(float) : 0;
+  return gemm_bf16_tn_supported(M, Na, Nb) ? tn_plan(M, Na, Nb, variant).ws_bytes(Na, Nb) : 0;
 }
 
 SALUN_EXPORT int salun_gemm_bf16_tn(const void *dy, const void *x, float *dw, int64_t M, int Na, int Nb, int accumulate,
                                     int variant, void *ws, size_t ws_bytes, salun_stream_t stream) {
-  if (!salun_gemm_bf16_tn_supported(M, Na, Nb) || !dy || !x || !dw || variant < 0 || variant > 3) return SALUN_EINVAL;
-  if (!salun_aligned16(dy) || !salun_aligned16(x) || !salun_aligned16(dw)) return SALUN_EINVAL;
-  const TnPlan p = tn_plan(M, Na, Nb, variant);
-  const size_t need = p.splits > 1 ? (size_t)p.splits * Na * Nb * sizeof(float) : 0;
-  if (need && (!ws || ws_bytes < need || !salun_aligned16(ws))) return SALUN_ENOSPC;
+  if (!dy || !x || !dw || !salun_aligned16(dy) || !salun_aligned16(x) || !salun_aligned16(dw)) return SALUN_EINVAL;
+  TnPlan p;
+  const int prc = plan_gemm_tn(M, Na, Nb, variant, ws && salun_aligned16(ws), ws_bytes, p);
+  if (prc != SALUN_OK) return prc;
   TnArgs g;
   g.dy = static_cast<const uint16_t *>(dy); g.x = static_cast<const uint16_t *>(x);
   g.out = p.splits > 1 ? static_cast<float *>(ws) : dw;
@@ -1807,6 +1679,30 @@ SALUN_EXPORT int salun_gemm_bf16_tn(const void *dy, const void *x, float *dw, in
                        accumulate);
     SALUN_LAUNCH_CHECK();
   }
+  return SALUN_OK;
+}
+
+SALUN_EXPORT int salun_gemm_bf16_route(int op, int64_t M, int N, int K, int variant, size_t ws_bytes, char *buf, size_t buflen,
+                                       int *nsplit) {
+  if (!buf || buflen < 1) return SALUN_EINVAL;
+  buf[0] = 0;
+  if (nsplit) *nsplit = 0;
+  int len, ns = 1;
+  if (op == SALUN_GEMM_BF16_NT) {
+    const NtPlan p = plan_gemm_nt(M, N, K, variant);
+    if (p.rc != SALUN_OK) return p.rc;
+    len = nt_label(buf, buflen, p);
+  } else if (op == SALUN_GEMM_BF16_TN) {  // (M, Na, Nb) = (M, N, K)
+    TnPlan p;
+    const int rc = plan_gemm_tn(M, N, K, variant, true, ws_bytes, p);
+    if (rc != SALUN_OK) return rc;
+    len = tn_label(buf, buflen, p);
+    ns = p.splits;
+  } else {
+    return SALUN_EINVAL;
+  }
+  if (len < 0 || (size_t)len >= buflen) { buf[0] = 0; return SALUN_ENOSPC; }
+  if (nsplit) *nsplit = ns;
   return SALUN_OK;
 }
 

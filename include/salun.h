@@ -958,6 +958,25 @@ int salun_cls_head_backward(const float *p /*dev*/, const float *pooled /*dev*/,
                             float *db /*dev or NULL*/, int accumulate_w, int accumulate_b, int64_t B, int C, int HW,
                             int K, salun_stream_t stream);
 
+/* ----------------------------------------------------------------- K24 --
+ * MaxPool2d(kernel_size=2, stride=2) of an fp32 NCHW tensor (csrc/salun_pool.hip).
+ * Replaces  nn.MaxPool2d(kernel_size=2, stride=2)  Classification/models/VGG_LTH.py:86  and its backward.
+ * x [NC, H, W] (contiguous; NC = batch * channels), y [NC, H/2, W/2], idx [NC, H/2, W/2] one byte per output:
+ * the selected position inside the window, 0 top-left, 1 top-right, 2 bottom-left, 3 bottom-right.
+ * Selection is that of torch.nn.functional.max_pool2d: scan in that order from (-inf, position 0), take a value
+ * when it is greater than the running maximum or is NaN — the first of equal maxima wins, a later NaN replaces an
+ * earlier one, +0 after -0 does not replace it.
+ * Backward writes EVERY element of dx exactly once: the selected position gets the window's dy, the other three
+ * +0.0.  One launch each, no atomics, no workspace; the same inputs give the same bits whatever the launch geometry.
+ * 16-byte loads / stores (two outputs per item) are used when W % 4 == 0 and all three bases are 16-byte aligned,
+ * one output per thread otherwise.  Indexing is 64-bit.
+ * SALUN_EINVAL (nothing is written): NC < 1, H or W odd or < 2, a NULL pointer, a float pointer off 4-byte
+ * alignment, dx == dy. */
+int salun_maxpool2x2_forward(const float *x /*dev*/, float *y /*dev, NC*H/2*W/2*/, uint8_t *idx /*dev, NC*H/2*W/2*/,
+                             int64_t NC, int H, int W, salun_stream_t stream);
+int salun_maxpool2x2_backward(const float *dy /*dev*/, const uint8_t *idx /*dev*/, float *dx /*dev, NC*H*W*/,
+                              int64_t NC, int H, int W, salun_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -219,6 +219,8 @@ SIGNATURES = {
     "salun_cls_head_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "salun_cls_head_forward": (c_int, [c_void_p] * 12 + [c_int64, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "salun_cls_head_backward": (c_int, [c_void_p] * 9 + [c_int, c_int, c_int64, c_int, c_int, c_int, c_void_p]),
+    "salun_maxpool2x2_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    "salun_maxpool2x2_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
 }
 
 _lib = None

@@ -165,10 +165,28 @@ def library_head_loss(model: nn.Module, x: torch.Tensor, target: torch.Tensor, m
     return loss, output.detach()
 
 
+def head_parts(model: nn.Module):
+    """(function x -> the [B, C, H, W] input of the model's average pool, its last nn.Linear), or None.  Two layouts:
+    a `features(x)` method with an `fc` layer (ResNetCifar), and an nn.Sequential named `features` behind the model's
+    `normalize` layer with a `classifier` layer (VGG); a model of the second kind may bring its own `feature_maps(x)`
+    (VGG's runs the fused BN / K24 path when that is switched on)."""
+    feats = getattr(model, "features", None)
+    if isinstance(feats, nn.Module):
+        linear = getattr(model, "classifier", None)
+        maps = getattr(model, "feature_maps", None)
+        if maps is None:
+            norm = getattr(model, "normalize", None)
+            maps = feats if norm is None else (lambda x: feats(norm(x)))
+    else:
+        linear, maps = getattr(model, "fc", None), feats
+    return (maps, linear) if callable(maps) and isinstance(linear, nn.Linear) else None
+
+
 def use_fused_head(model: nn.Module, flag: bool = True) -> nn.Module:
     """Route `model.forward_loss(x, target, meters)` through K23.  The model needs `features(x)` (the [B, C, H, W]
-    input of its average pool) and an `fc` nn.Linear, as ResNetCifar has."""
-    if flag and not (callable(getattr(model, "features", None)) and isinstance(getattr(model, "fc", None), nn.Linear)):
+    input of its average pool) and an `fc` nn.Linear, as ResNetCifar has, or a `features` nn.Sequential and a
+    `classifier` nn.Linear, as VGG has."""
+    if flag and head_parts(model) is None:
         raise TypeError(f"use_fused_head: {type(model).__name__} has no features() / fc pair")
     model.fused_head = bool(flag)
     return model
@@ -178,5 +196,6 @@ def forward_loss(model: nn.Module, x: torch.Tensor, target: torch.Tensor, meters
                  criterion=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """(loss, logits.detach()) of one batch: K23 when `use_fused_head(model)` was called, else the library head."""
     if getattr(model, "fused_head", False):
-        return fused_cls_head(model.features(x), model.fc, target, meters)
+        maps, linear = head_parts(model)
+        return fused_cls_head(maps(x), linear, target, meters)
     return library_head_loss(model, x, target, meters, criterion)

@@ -165,11 +165,17 @@ _GN_TYPES = {nn.GroupNorm}
 
 
 def use_fused_bn(model: nn.Module, blocks: bool = True) -> int:
-    """Switch this package's CIFAR ResNet (stem + BasicBlocks) to the fused BN path; with `blocks` each BasicBlock
-    additionally runs as one autograd node (resblock.py).  Returns the number of BatchNorm layers covered."""
+    """Switch this package's CIFAR ResNet (stem + BasicBlocks) or VGG to the fused BN path; with `blocks` each BasicBlock
+    additionally runs as one autograd node (resblock.py).  A VGG also runs its MaxPool2d(2, 2) entries on K24
+    (pool.py).  Returns the number of BatchNorm layers covered."""
     from .Classification.models import resnet_cifar as R
+    from .Classification.models import vgg_lth as V
     n = 0
     for mod in model.modules():
+        if isinstance(mod, V.VGG):
+            mod.fused_bn = True
+            n += sum(isinstance(m, nn.BatchNorm2d) for m in mod.features)
+            continue
         if isinstance(mod, R.BasicBlock):
             mod.fused_bn = True
             mod.fused_block = bool(blocks)

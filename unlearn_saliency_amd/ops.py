@@ -1127,3 +1127,26 @@ def prune_count_zeros(p: torch.Tensor, segs: torch.Tensor, n_sel: int) -> torch.
                                              _dev(segs, torch.int64, "segs"), c_int(segs.shape[0]), c_int64(n_sel),
                                              c_void_p(out.data_ptr()), _stream()), "salun_prune_count_zeros")
     return out
+
+
+# ----------------------------------------------------------------------------- K24
+def maxpool2x2_forward(x: torch.Tensor):
+    """MaxPool2d(2, 2) of x[N, C, H, W] (H, W even) -> (y [N, C, H/2, W/2], idx uint8 of the same shape: the selected
+    position 0..3 inside each window)."""
+    N, C, H, W = x.shape
+    y = torch.empty((N, C, H // 2, W // 2), dtype=torch.float32, device=x.device)
+    idx = torch.empty((N, C, H // 2, W // 2), dtype=torch.uint8, device=x.device)
+    check(_lib.lib().salun_maxpool2x2_forward(_dev(x, torch.float32, "x"), c_void_p(y.data_ptr()),
+                                              c_void_p(idx.data_ptr()), c_int64(N * C), H, W, _stream()),
+          "salun_maxpool2x2_forward")
+    return y, idx
+
+
+def maxpool2x2_backward(dy: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """dx [N, C, 2P, 2Q] of dy[N, C, P, Q]: every element written once (dy at the selected position, +0 elsewhere)."""
+    N, C, P, Q = dy.shape
+    dx = torch.empty((N, C, 2 * P, 2 * Q), dtype=torch.float32, device=dy.device)
+    check(_lib.lib().salun_maxpool2x2_backward(_dev(dy, torch.float32, "dy"), _dev(idx, torch.uint8, "idx"),
+                                               c_void_p(dx.data_ptr()), c_int64(N * C), 2 * P, 2 * Q, _stream()),
+          "salun_maxpool2x2_backward")
+    return dx

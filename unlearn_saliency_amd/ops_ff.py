@@ -37,9 +37,13 @@ def conv_sq(x: torch.Tensor, dy: torch.Tensor, w: torch.Tensor, F: torch.Tensor,
         raise NotImplementedError(f"ff conv_sq: {tuple(x.shape)} -> {tuple(dy.shape[1:])} with a {R}x{R} filter is "
                                   "outside the backward-weight kernels' domain")
     ws = ops.workspace(nbytes, x.device)
-    check(L.salun_ff_conv_sq(_dev(x, torch.float32, "x"), _dev(dy, torch.float32, "dy"), _dev(w, torch.float32, "w"),
-                             _dev(F, torch.float32, "F"), G, B, C, H, W, K, R, stride, pad, P, Q,
-                             _dev(ws, torch.uint8, "ws"), nbytes, _stream()), "salun_ff_conv_sq")
+    rc = L.salun_ff_conv_sq(_dev(x, torch.float32, "x"), _dev(dy, torch.float32, "dy"), _dev(w, torch.float32, "w"),
+                            _dev(F, torch.float32, "F"), G, B, C, H, W, K, R, stride, pad, P, Q,
+                            _dev(ws, torch.uint8, "ws"), nbytes, _stream())
+    if rc == _lib.SALUN_EINVAL:  # the workspace query is by size alone; the launch itself refuses e.g. 2x2 maps
+        raise NotImplementedError(f"ff conv_sq: {tuple(x.shape)} -> {tuple(dy.shape[1:])} with a {R}x{R} filter is "
+                                  "outside the backward-weight kernels' domain")
+    check(rc, "salun_ff_conv_sq")
 
 
 def linear_sq(x: torch.Tensor, dy: torch.Tensor, w: torch.Tensor, F: torch.Tensor) -> None:

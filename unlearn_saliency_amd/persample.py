@@ -188,8 +188,11 @@ def persample_dots(model: nn.Module, x: torch.Tensor, y: torch.Tensor, u0: torch
         P, Q = dy.shape[2], dy.shape[3]
         y2 = ops.conv2d_forward(xin.contiguous(), w2, b2, mod.stride[0], mod.padding[0], P, Q)
         if y2 is None:
-            raise RuntimeError(f"persample: the tangent convolution {tuple(xin.shape)} * {tuple(w2.shape)} is outside "
-                               "the convolution kernels' domain")
+            # outside the convolution kernels' domain (an RGB input with a bias: VGG's first layer): the library
+            # convolution, counted like every other one (conv.LIBRARY_CONV_CALLS; an error under conv.strict)
+            from .conv import _fallback
+            _fallback("shape", f"persample tangent convolution {tuple(xin.shape)} * {tuple(w2.shape)}")
+            y2 = F.conv2d(xin, w2, b2, mod.stride[0], mod.padding[0]).contiguous()
         ops_iu.conv_dot(y2, dy, out)
     return out
 
@@ -266,6 +269,16 @@ def _fisher_square(records: list, w: torch.Tensor, B: int, F_acc: torch.Tensor, 
                 raise NotImplementedError(f"fisher_diag: Linear input of shape {tuple(xin.shape)} (only (B, K))")
             ops_ff.linear_sq(x0, dy, w, sl(F_acc, wt))
         else:
-            ops_ff.conv_sq(x0, dy, w, sl(F_acc, wt), mod.stride[0], mod.padding[0])
+            try:
+                ops_ff.conv_sq(x0, dy, w, sl(F_acc, wt), mod.stride[0], mod.padding[0])
+            except NotImplementedError:
+                # outside the backward-weight kernels' domain (2x2 feature maps: VGG's last block): one library
+                # backward-weight per class group, counted like every other one (conv.LIBRARY_CONV_CALLS)
+                from .conv import _fallback
+                _fallback("backward", f"fisher_diag backward-weight {tuple(x0.shape)} * {tuple(wt.shape)}")
+                Fw = sl(F_acc, wt)
+                for g in range(w.numel()):
+                    s = torch.nn.grad.conv2d_weight(x0, wt.shape, dy[g * B:(g + 1) * B], mod.stride, mod.padding)
+                    Fw.add_(w[g] * s * s)
         if b is not None:
             ops_ff.vec_sq(dy, w, sl(F_acc, b), B)

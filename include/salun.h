@@ -378,7 +378,8 @@ int salun_conv3x3_packed(const float *x /*dev*/, const float *img /*dev*/, const
  * fp32 OIHW in the flat arena and `salun_conv2d_bf16_pack_weights` writes the bf16 image wp[K][R*R][C] both
  * data kernels read (backward-data reads it transposed, no second image).  Square filter R in {1,3}, stride in
  * {1,2}, symmetric padding <= R-1, C % 32 == 0, K % 32 == 0, 16-B aligned pointers;
- * anything else returns SALUN_EINVAL (`salun_conv2d_bf16_supported` answers without launching).
+ * anything else returns SALUN_EINVAL (`salun_conv2d_bf16_supported` answers without launching), and so does every
+ * direction for an empty batch or extent (N, H, W, OH or OW < 1).
  *   forward         y = conv(x, w) + bias[k] + nbias[n][k] + addend[n][oh][ow][k]   (each optional, fp32 / fp32 / bf16)
  *   backward_data   dx = conv_transpose(dy, w) + addend[n][h][w][c]
  *   backward_weight dw[K][C][R][R] fp32 (= or +=): sum over pixels of dy * x, pixel range split over workgroups ->

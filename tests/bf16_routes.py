@@ -2,7 +2,8 @@
 (csrc/salun_conv_bf16.hip: convolution forward / backward-data / backward-weight) and K16 (csrc/salun_gemm.hip: the NT and
 TN GEMMs, the ring form of the convolution forward), written from the code as it stood BEFORE the plans moved into
 csrc/salun_bf16_plan.h - entry-point checks, the ring probe, dispatch_igemm / launch_igemm, tn_route, wgrad_splits, the
-13-arm switch of salun_gemm_bf16_nt - in a default build (no tile pin, default split targets).
+13-arm switch of salun_gemm_bf16_nt - in a default build (no tile pin, default split targets).  One check is later than that:
+backward-weight refuses an empty input or output extent, as the data kernels always have.
 test_bf16_routes_cpu.py holds it, label for label, to salun_conv2d_bf16_route / salun_gemm_bf16_route and to the
 library's workspace and *_supported queries.
 
@@ -191,6 +192,8 @@ def wgrad_workspace_bytes(shape, tn=1):
 def backward_weight(shape, ws_bytes=0, aligned=True, tn=1):
     N, H, W, C, K, R, stride, pad = shape
     if N < 1 or not conv_supported(C, K, R, stride, pad):
+        return None
+    if H < 1 or W < 1 or _out(H, R, stride, pad) < 1 or _out(W, R, stride, pad) < 1:  # no pixel to reduce over
         return None
     if ws_bytes < wgrad_workspace_bytes(shape, tn):
         return ENOSPC

@@ -1,7 +1,8 @@
-"""The guarded device arena of the exact-answer GPU tests (test_conv_exact_gpu.py, test_gemm_exact_gpu.py): every tensor
-of a call lies 16-byte aligned in ONE flat allocation with GUARD floats of NaN before and after every input and of a
-sentinel pattern around every output (and in the output itself before the call); after the call everything but the
-outputs must hold the bits it was given."""
+"""The guarded device arena of the exact-answer GPU tests (test_conv_exact_gpu.py, test_gemm_exact_gpu.py,
+test_conv_bf16_exact_gpu.py): every tensor of a call lies 16-byte aligned in ONE flat allocation with GUARD floats of NaN
+before and after every input and of a sentinel pattern around every output (and in the output itself before the call);
+after the call everything but the outputs must hold the bits it was given.  A part is fp32 (4-byte words) or, with
+dtype="bf16", bf16 (two elements per word, an even number of them); guards, alignment and skew are in words either way."""
 from ctypes import c_void_p
 
 import torch
@@ -10,19 +11,33 @@ GUARD = 4096
 NAN_BITS, SENTINEL = 0x7FC00000, 0x7FA5A5A5      # a quiet NaN; a NaN pattern no computation produces
 
 
+def _bf16_words(data):
+    """bf16 data (a float tensor, rounded to bf16, or int16 bit patterns) as the int32 words that hold it."""
+    flat = data.reshape(-1)
+    if flat.dtype != torch.int16:
+        flat = flat.float().bfloat16().view(torch.int16)
+    return flat.contiguous().view(torch.int32)
+
+
 class Arena:
     """The tensors of one call inside one flat device allocation, each behind and before GUARD floats."""
 
     def __init__(self):
-        self.parts, self.fills, self.n = {}, [], 0
+        self.parts, self.fills, self.n, self.bf16 = {}, [], 0, set()
 
-    def put(self, name, data=None, shape=None, out=False, skew=0):
+    def put(self, name, data=None, shape=None, out=False, skew=0, dtype="f32"):
         """An input (data given), an output (shape given; filled with the sentinel) or an in-place output (both).
-        skew: floats off the 16-byte boundary."""
+        skew: floats off the 16-byte boundary.  dtype "bf16": 2-byte elements (parts[name] counts its 4-byte words)."""
         shape = tuple(data.shape) if data is not None else tuple(shape)
         numel = 1
         for s in shape:
             numel *= s
+        assert dtype in ("f32", "bf16")
+        if dtype == "bf16":
+            assert numel % 2 == 0, "a bf16 part holds whole words"
+            numel //= 2
+            self.bf16.add(name)
+            data = None if data is None else _bf16_words(data)
         start = self.n + GUARD + skew
         end = (start + numel + 3) // 4 * 4
         self.fills.append((self.n, end + GUARD, SENTINEL if out else NAN_BITS, start, data))
@@ -57,6 +72,8 @@ class Arena:
     def part(self, after, name):
         """The output `name` of a downloaded arena."""
         start, numel, shape, _ = self.parts[name]
+        if name in self.bf16:                      # bf16 bits
+            return after[start:start + numel].view(torch.int16).view(shape)
         return after[start:start + numel].view(torch.float32).view(shape)
 
     def result(self, name):
@@ -65,12 +82,14 @@ class Arena:
 
     def restore(self, **outputs):
         """The arena as uploaded, for another call on the same inputs; outputs named here start from the given contents
-        (a float tensor, an int32 bit pattern, or None for the sentinel)."""
+        (a float tensor, an int32 bit pattern - int16 for a bf16 part -, or None for the sentinel)."""
         for name, data in outputs.items():
             start, numel, _, out = self.parts[name]
             assert out
             if data is None:
                 self.host[start:start + numel] = SENTINEL
+            elif name in self.bf16:
+                self.host[start:start + numel] = _bf16_words(data)
             else:
                 flat = data.reshape(-1)
                 self.host[start:start + numel] = flat if flat.dtype == torch.int32 else flat.float().view(torch.int32)

@@ -3,7 +3,7 @@ instruction against the library fp32 convolution evaluated on the SAME bf16-roun
 
 Tolerance: products of bf16 values are exact in fp32 and both sides accumulate in fp32, so the two differ by
 summation order (~1e-6 relative to the reduction's magnitude) plus, for the bf16 outputs (forward, backward-data), the
-final rounding to bf16 (relative 2^-9).  Asserted: |got - ref| <= 2^-8 * |ref| + 1e-5 * max|ref| for bf16 outputs,
+final rounding to bf16 (relative 2^-8: 8 significand bits).  Asserted: |got - ref| <= 2^-8 * |ref| + 1e-5 * max|ref| for bf16 outputs,
 <= 2e-5 * max|ref| for the fp32 weight gradient.
 """
 import pytest

@@ -344,6 +344,9 @@ inline WgradPlan plan_conv_wgrad(int N, int H, int W, int C, int K, int R, int s
     p.tn = dw_al16;
     if (p.tn) p.lay = tn;
   }
+  // an empty input or output extent (H < R - 2 * pad) is refused as forward and backward-data refuse it: there is no pixel
+  // to reduce over, and the column sums would walk N * OH * OW rows of a dy that has none
+  if (H < 1 || W < 1 || p.OH < 1 || p.OW < 1) return p;
   if (ws_bytes < p.need) { p.rc = SALUN_ENOSPC; return p; }
   if (!p.tn) {
     // conv_bf16_wgrad's buffer descriptors: an out-of-image lane reads at byte offset 2^31, past the end of both tensors

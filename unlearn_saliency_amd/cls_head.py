@@ -10,7 +10,7 @@
                                                  `model(x)` is unchanged
 
 The backward honours the incoming scalar gradient (loss sign, data-parallel shard scale) and adds the fc gradients
-straight into the flat arena when `gradsink.sink` gives a destination, exactly as `gemm._Linear.backward` does.
+straight into the flat arena when `gradsink.dest` says they can go there, exactly as `gemm._Linear.backward` does.
 fp32 device tensors only: anything else is an error, not a fall-back.
 """
 from __future__ import annotations
@@ -111,6 +111,9 @@ def head_backward(p: torch.Tensor, pooled: torch.Tensor, weight: torch.Tensor, t
     return dlogits
 
 
+_NO_GRAD = gradsink.Dest(None, False)  # a parameter that needs no gradient: the kernel skips it, autograd gets None
+
+
 class _ClsHead(FastFunction):
     @staticmethod
     def forward(ctx, x, weight, bias, target, meters):
@@ -129,15 +132,10 @@ class _ClsHead(FastFunction):
         if g.dtype != torch.float32 or not g.is_cuda:
             g = g.to(device=p.device, dtype=torch.float32)
         dx = torch.empty(ctx.xshape, dtype=torch.float32, device=p.device) if ctx.needs_input_grad[0] else None
-        dw = db = sink_w = sink_b = None
-        if ctx.needs_input_grad[1]:
-            sink_w = gradsink.sink(ctx.params[0])
-            dw = sink_w if sink_w is not None else torch.empty_like(weight)
-        if ctx.needs_input_grad[2]:
-            sink_b = gradsink.sink(ctx.params[1])
-            db = sink_b if sink_b is not None else torch.empty(weight.shape[0], dtype=torch.float32, device=p.device)
-        head_backward(p, pooled, weight, target, g, H * W, dx, dw, db, sink_w is not None, sink_b is not None)
-        return dx, (None if sink_w is not None else dw), (None if sink_b is not None else db), None, None
+        dw = gradsink.dest(ctx.params[0], torch.empty) if ctx.needs_input_grad[1] else _NO_GRAD
+        db = gradsink.dest(ctx.params[1], torch.empty) if ctx.needs_input_grad[2] else _NO_GRAD
+        head_backward(p, pooled, weight, target, g, H * W, dx, dw.out, db.out, dw.accumulate, db.accumulate)
+        return dx, dw.returned(), db.returned(), None, None
 
 
 def fused_cls_head(x4d: torch.Tensor, fc: nn.Linear, target: torch.Tensor, meters: Optional[HeadMeters] = None

@@ -18,7 +18,6 @@ from .fastfn import FastFunction
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import dist as sdist
 from . import gradsink, ops, ringpack, wgrad_side
 
 
@@ -82,21 +81,21 @@ class _ConvFn(FastFunction):
         stride, pad = ctx.stride, ctx.pad
         dx = dw = db = None
         if ctx.needs_input_grad[1]:
-            dst = gradsink.sink(ctx.weight_param) if ctx.native else None
+            # (a forward that ran on the library leaves backward to the library too: nothing of ours to sink into)
+            d = gradsink.dest(ctx.weight_param, when=ctx.native)
             # the weight gradient goes straight into .grad (gradsink): nothing on the main stream consumes it before
             # the end of the backward pass, so it can run on the side stream next to backward-data (wgrad_side.py)
-            if dst is not None and wgrad_side.OVERLAP:
+            if d.accumulate and wgrad_side.OVERLAP:
                 dw = wgrad_side.beside(dy.device, (x, dy), lambda side: ops.conv2d_backward_weight(
-                    x, dy, w.shape, stride, pad, out=dst, accumulate=True, shared=True, stream=side))
+                    x, dy, w.shape, stride, pad, out=d.out, accumulate=True, shared=True, stream=side))
             # (None after the side-stream attempt: outside the kernel's domain, nothing was launched)
-            if dw is None:
-                dw = ops.conv2d_backward_weight(x, dy, w.shape, stride, pad, out=dst, accumulate=True) if ctx.native else None
+            if dw is None and ctx.native:
+                dw = ops.conv2d_backward_weight(x, dy, w.shape, stride, pad, out=d.out, accumulate=d.accumulate)
             if dw is None:
                 _fallback("backward", f"backward-weight {tuple(x.shape)} * {tuple(w.shape)}")
                 dw = torch.nn.grad.conv2d_weight(x, w.shape, dy, stride, pad)
-            elif dst is not None:  # already added into w.grad by the kernel
-                gradsink.arrived(w)
-                dw = None
+            else:
+                dw = d.returned(dw)
         if ctx.needs_input_grad[0]:
             dx = ops.conv2d_backward_data(dy, w, x.shape, stride, pad) if ctx.native else None
             if dx is None:
@@ -105,12 +104,8 @@ class _ConvFn(FastFunction):
         if ctx.has_bias and ctx.needs_input_grad[2]:
             # own streaming kernel instead of ATen's generic reduction; added straight into bias.grad when that is a
             # plain view of the flat arena (no AccumulateGrad launch)
-            bdst = gradsink.sink(ctx.bias_param)
-            if bdst is not None:
-                ops.channel_sum(dy, out=bdst, accumulate=True)
-                gradsink.arrived(ctx.bias_param)
-            else:
-                db = ops.channel_sum(dy)
+            d = gradsink.dest(ctx.bias_param)
+            db = d.returned(ops.channel_sum(dy, out=d.out, accumulate=d.accumulate))
         return dx, dw, db, None, None, None, None
 
 

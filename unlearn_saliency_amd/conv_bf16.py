@@ -16,7 +16,7 @@ run on the fp32 MFMA kernels of conv.py; nothing here calls the library convolut
 """
 from __future__ import annotations
 
-import os as _os_env
+import os
 import weakref as _weakref
 
 import torch
@@ -38,6 +38,29 @@ def _can_overlap() -> bool:
     backward pass: they are issued on the backward-weight side stream (wgrad_side.beside), next to the input-gradient
     kernels of this and the following layers — at batch 8 most of the SD U-Net's kernels leave CUs idle."""
     return wgrad_side.OVERLAP and not torch.cuda.is_current_stream_capturing()
+
+
+def _weight_bias_grad(mod, has_bias, xn, dyn, wshape, s, p, dnb=None):
+    """ONE backward-weight call for dW, db and (`dnb`, fp32 [N, K]) the per-image channel sums of dy, over NHWC bf16 views
+    (a Linear layer's tokens included); returns (dw, db) as autograd gets them: None for what was added into `.grad`."""
+    to_w = gradsink.dest(mod.weight)
+    # the kernel has ONE accumulate flag for dw and db: without a weight sink it overwrites both outputs, so the bias
+    # gradient must not target bias.grad then (it would be overwritten, not accumulated) — it goes through autograd
+    # like dw; with a weight sink but no bias sink, db accumulates into fresh zeros
+    to_b = gradsink.dest(mod.bias, torch.zeros, when=to_w.accumulate) if has_bias else None
+    all_in_grad = to_w.accumulate and (to_b is None or to_b.accumulate)
+    bias_out = to_b.out if has_bias else None
+    if all_in_grad and _can_overlap():
+        # everything the backward-weight call writes lands in .grad storage: side stream; dnb is read by autograd on THIS
+        # stream right away, so its (small) sums are a launch of their own here
+        if dnb is not None:
+            ops.colsum_bf16(dyn, dyn.shape[0], nbias_out=dnb)
+        wgrad_side.beside(dyn.device, (xn, dyn), lambda side: ops.conv2d_bf16_backward_weight(
+            xn, dyn, wshape, s, p, out=to_w.out, accumulate=True, bias_out=bias_out, stream=side))
+        return None, None
+    got = ops.conv2d_bf16_backward_weight(xn, dyn, wshape, s, p, out=to_w.out, accumulate=to_w.accumulate,
+                                          bias_out=bias_out, nbias_out=dnb)
+    return to_w.returned(got), (to_b.returned() if has_bias else None)
 
 
 class _ConvBF16Fn(FastFunction):
@@ -62,30 +85,10 @@ class _ConvBF16Fn(FastFunction):
         dyn = _nhwc(dy)
         dx = dw = db = dnb = dadd = None
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            dst = gradsink.sink(mod.weight)  # the Parameter itself
-            # the kernel has ONE accumulate flag for dw and db: without a weight sink it overwrites both outputs, so
-            # the bias gradient must not target bias.grad then (it would be overwritten, not accumulated) — it goes
-            # through autograd like dw; with a weight sink but no bias sink, db accumulates into fresh zeros
-            bdst = gradsink.sink(mod.bias) if (ctx.has_bias and dst is not None) else None
-            if ctx.has_bias and bdst is None:
-                bdst = torch.zeros(wshape[0], dtype=torch.float32, device=dyn.device)
-                db = bdst
             if ctx.nbias and ctx.needs_input_grad[4] and dyn.shape[0] <= 128:
                 # per-image channel sums of dy out of the bias gradient's partial sums (one kernel pair for both)
                 dnb = torch.empty((dyn.shape[0], wshape[0]), dtype=torch.float32, device=dyn.device)
-            if dst is not None and db is None and _can_overlap():
-                # everything the backward-weight call writes lands in .grad storage: side stream; dnb is read by autograd
-                # on THIS stream right away, so its (small) sums are a launch of their own here
-                if dnb is not None:
-                    ops.colsum_bf16(dyn, dyn.shape[0], nbias_out=dnb)
-                wgrad_side.beside(dyn.device, (xn, dyn),
-                                  lambda side: ops.conv2d_bf16_backward_weight(xn, dyn, wshape, s, p, out=dst,
-                                                                               accumulate=True, bias_out=bdst, stream=side))
-            else:
-                got = ops.conv2d_bf16_backward_weight(xn, dyn, wshape, s, p, out=dst, accumulate=True, bias_out=bdst,
-                                                      nbias_out=dnb)
-                if dst is None:
-                    dw = got
+            dw, db = _weight_bias_grad(mod, ctx.has_bias, xn, dyn, wshape, s, p, dnb)
         if ctx.needs_input_grad[0]:
             dx = ops.conv2d_bf16_backward_data(dyn, mod.packed_weight(), tuple(xn.shape), R, s, p).permute(0, 3, 1, 2)
             if dx.dtype != ctx.x_dtype:
@@ -105,7 +108,7 @@ class _ConvBF16Fn(FastFunction):
 # images of that device in ceil(n / 64) launches (csrc: k_pack_jobs).  A module that was never registered (built by hand
 # in a test) packs alone, as before.  No event orders a pack against other streams: SD/train_scripts.forget_and_target
 # watches PACK_LAUNCHES instead and keeps the target pass on the main stream when the forget pass packed anything.
-BATCH_PACKS = [_os_env.environ.get("SALUN_BF16_BATCH_PACK", "1") != "0"]  # A/B switch: False = one launch per image at its first use
+BATCH_PACKS = [os.environ.get("SALUN_BF16_BATCH_PACK", "1") != "0"]  # A/B switch: False = one launch per image at its first use
 PACK_LAUNCHES = weightimg.BF16_LAUNCHES
 # (the ops.* seams are looked up per call: host tests replace them)
 _IMAGES = weightimg.Registry(lambda jobs: ops.bf16_pack_batch(jobs), PACK_LAUNCHES, per_device=True, batching=BATCH_PACKS)
@@ -175,8 +178,7 @@ def _tokens_nhwc(t: torch.Tensor, C: int) -> torch.Tensor:
 
 
 # SALUN_LINEAR_GEMM=0: keep the Linear layers on the K11 1x1 convolution kernels (A/B switch)
-import os as _os
-_USE_K16 = [_os.environ.get("SALUN_LINEAR_GEMM", "1") != "0"]
+_USE_K16 = [os.environ.get("SALUN_LINEAR_GEMM", "1") != "0"]
 
 
 def _al16(t) -> bool:
@@ -200,8 +202,8 @@ class _LinearBF16Fn(FastFunction):
         if k16:
             y = ops.gemm_bf16_nt(x2, mod.packed_weight().view(K, C), bias, a2)
         else:
-            xn = x2.view(1, M // 8, 8, C) if M % 8 == 0 else x2.view(1, M, 1, C)
-            an = a2.view(1, xn.shape[1], xn.shape[2], K) if a2 is not None else None
+            xn = _tokens_nhwc(x2, C)
+            an = _tokens_nhwc(a2, K) if a2 is not None else None
             y = ops.conv2d_bf16_forward(xn, mod.packed_weight(), 1, 1, 0, bias=bias, nbias=None, addend=an)
         ctx.save_for_backward(x2)
         ctx.w_shape = (K, C)
@@ -215,30 +217,19 @@ class _LinearBF16Fn(FastFunction):
         mod = ctx.mod
         K, C = ctx.w_shape
         M = x2.shape[0]
-        dy2 = dy.to(torch.bfloat16).contiguous().view(M, K)
-        as_img = lambda t, ch: t.view(1, M // 8, 8, ch) if M % 8 == 0 else t.view(1, M, 1, ch)
+        dyn = _tokens_nhwc(dy, K)
         dx = dw = db = dadd = None
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            dst = gradsink.sink(mod.weight)
-            bdst = gradsink.sink(mod.bias) if (ctx.has_bias and dst is not None) else None
-            if ctx.has_bias and bdst is None:
-                bdst = torch.zeros(K, dtype=torch.float32, device=dy2.device)
-                db = bdst
-            launch = lambda side=None: ops.conv2d_bf16_backward_weight(
-                as_img(x2, C), as_img(dy2, K), (K, C, 1, 1), 1, 0, out=dst.view(K, C, 1, 1) if dst is not None else None,
-                accumulate=True, bias_out=bdst, stream=side)
-            if dst is not None and db is None and _can_overlap():
-                wgrad_side.beside(dy2.device, (x2, dy2), launch)
-            else:
-                got = launch()
-                if dst is None:
-                    dw = got.view(K, C)
+            dw, db = _weight_bias_grad(mod, ctx.has_bias, _tokens_nhwc(x2, C), dyn, (K, C, 1, 1), 1, 0)
+            if dw is not None:
+                dw = dw.view(K, C)
         if ctx.needs_input_grad[0]:
+            dy2 = dyn.view(M, K)
             if _USE_K16[0] and ops.gemm_bf16_supported(M, C, K) and _al16(dy2):
                 dx = ops.gemm_bf16_nt(dy2, mod.packed_weight_t()).view(ctx.x_shape)
             else:
-                dx = ops.conv2d_bf16_backward_data(as_img(dy2, K), mod.packed_weight(), (1,) + tuple(as_img(x2, C).shape[1:]),
-                                                   1, 1, 0).view(ctx.x_shape)
+                dx = ops.conv2d_bf16_backward_data(dyn, mod.packed_weight(), tuple(_tokens_nhwc(x2, C).shape), 1, 1, 0
+                                                   ).view(ctx.x_shape)
             if dx.dtype != ctx.x_dtype:
                 dx = dx.to(ctx.x_dtype)
         if ctx.addend_dtype is not None and ctx.needs_input_grad[4]:

@@ -178,17 +178,14 @@ class _Linear(FastFunction):
             dx = dx.view(ctx.xshape)
         if ctx.needs_input_grad[1]:
             # dW[n, k] = sum_m dY[m, n] x[m, k], added straight into the flat gradient when it can be
-            sink = gradsink.sink(ctx.params[0])
-            dst = sink if sink is not None else torch.empty_like(weight)
-            launch([Job(dst.data_ptr(), N, K, dst.stride(0),
+            d = gradsink.dest(ctx.params[0], torch.empty)
+            launch([Job(d.out.data_ptr(), N, K, d.out.stride(0),
                         [Seg(dy2.data_ptr(), 1, dy2.stride(0), x2.data_ptr(), 1, x2.stride(0), x2.shape[0])],
-                        accumulate=sink is not None)], dy.device)
-            dw = None if sink is not None else dst
+                        accumulate=d.accumulate)], dy.device)
+            dw = d.returned()
         if bias is not None and ctx.needs_input_grad[2]:
-            sink = gradsink.sink(ctx.params[1])
-            db = colsum(dy2, out=sink, accumulate=sink is not None)
-            if sink is not None:
-                db = None
+            d = gradsink.dest(ctx.params[1])
+            db = d.returned(colsum(dy2, out=d.out, accumulate=d.accumulate))
         return dx, dw, db
 
 
@@ -260,24 +257,20 @@ class _GroupedLinear(FastFunction):
         for g, dy in live:
             if not ctx.needs_input_grad[1 + g]:
                 continue
-            sink = gradsink.sink(ctx.weights[g])
-            dst = sink if sink is not None else torch.empty_like(ws[g])
-            keep.append(dst)
-            jobs.append(Job(dst.data_ptr(), ws[g].shape[0], K, dst.stride(0),
+            d = gradsink.dest(ctx.weights[g], torch.empty)
+            keep.append(d.out)
+            jobs.append(Job(d.out.data_ptr(), ws[g].shape[0], K, d.out.stride(0),
                             [Seg(dy.data_ptr(), 1, dy.stride(0), x2.data_ptr(), 1, x2.stride(0), M)],
-                            accumulate=sink is not None))
-            if sink is None:
-                dws[g] = dst
+                            accumulate=d.accumulate))
+            dws[g] = d.returned()
         for j0 in range(0, len(jobs), _lib.SALUN_GEMM_MAX_JOBS):
             launch(jobs[j0:j0 + _lib.SALUN_GEMM_MAX_JOBS], x2.device)
         for g, dy in live:
             b = bs[g]
             if b is None or not ctx.needs_input_grad[1 + G + g]:
                 continue
-            sink = gradsink.sink(b)
-            r = colsum(dy, out=sink, accumulate=sink is not None)
-            if sink is None:
-                dbs[g] = r
+            d = gradsink.dest(b)
+            dbs[g] = d.returned(colsum(dy, out=d.out, accumulate=d.accumulate))
         return (dx, *dws, *dbs)
 
 

@@ -34,16 +34,10 @@ class _FusedBN(FastFunction):
     def backward(ctx, dy):
         x, y, weight, bias, mean, invstd = ctx.saved_tensors
         training, relu, has_res = ctx.cfg
-        gw, gb = gradsink.sink(ctx.params[0]), gradsink.sink(ctx.params[1])
-        if gw is None or gb is None:
-            gw = gb = None
+        dg, db = gradsink.pair(*ctx.params)
         dx, dres, dgamma, dbeta = ops.bn_backward(_grad_on_grid(dy), y, x, weight, mean, invstd, training, relu,
-                                                  has_res and ctx.needs_input_grad[3], gw, gb)
-        if gw is not None:
-            gradsink.arrived(weight)
-            gradsink.arrived(bias)
-            dgamma = dbeta = None
-        return dx, dgamma, dbeta, dres, None, None, None, None, None, None, None
+                                                  has_res and ctx.needs_input_grad[3], dg.out, db.out)
+        return dx, dg.returned(dgamma), db.returned(dbeta), dres, None, None, None, None, None, None, None
 
 
 def _on_grid(t: torch.Tensor) -> bool:
@@ -96,13 +90,9 @@ class _FusedGN(FastFunction):
     def backward(ctx, dz):
         x, weight, bias, mean, rstd = ctx.saved_tensors
         groups, silu = ctx.cfg
-        gw, gb = gradsink.sink(ctx.params[0]), gradsink.sink(ctx.params[1])
-        if gw is None or gb is None:
-            gw = gb = None
-        dx, dgamma, dbeta = ops.gn_backward(_grad_on_grid(dz), x, weight, bias, mean, rstd, groups, silu, gw, gb)
-        if gw is not None:
-            dgamma = dbeta = None
-        return dx, dgamma, dbeta, None, None, None
+        dg, db = gradsink.pair(*ctx.params)
+        dx, dgamma, dbeta = ops.gn_backward(_grad_on_grid(dz), x, weight, bias, mean, rstd, groups, silu, dg.out, db.out)
+        return dx, dg.returned(dgamma), db.returned(dbeta), None, None, None
 
 
 class _FusedGN16(FastFunction):
@@ -128,12 +118,9 @@ class _FusedGN16(FastFunction):
         weight, bias = ctx.params
         groups, silu = ctx.cfg
         dyn = dy.to(torch.bfloat16).contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1)
-        gw, gb = gradsink.sink(ctx.params[0]), gradsink.sink(ctx.params[1])
-        sunk = gw is not None and gb is not None
-        if not sunk:
-            gw, gb = torch.empty_like(weight), torch.empty_like(bias)
-        dx = ops.gn_bf16_backward(dyn, xn, weight, mr, ab, groups, silu, gw, gb, accumulate=sunk)
-        return dx.permute(0, 3, 1, 2), (None if sunk else gw), (None if sunk else gb), None, None, None
+        dg, db = gradsink.pair(weight, bias, torch.empty)
+        dx = ops.gn_bf16_backward(dyn, xn, weight, mr, ab, groups, silu, dg.out, db.out, accumulate=dg.accumulate)
+        return dx.permute(0, 3, 1, 2), dg.returned(), db.returned(), None, None, None
 
 
 _FUSED_GN = True

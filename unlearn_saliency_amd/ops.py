@@ -855,17 +855,14 @@ class _LayerNorm16(FastFunction):
         dyc = dy.to(torch.bfloat16).contiguous()
         L = _lib.lib()
         ws = workspace(_q("salun_ln_bf16_workspace_bytes", rows, C), xc.device)
-        gw, gb = gradsink.sink(ctx.params[0]), gradsink.sink(ctx.params[1])
-        sunk = gw is not None and gb is not None
-        if not sunk:
-            gw, gb = torch.empty_like(weight), torch.empty_like(bias)
+        dg, db = gradsink.pair(weight, bias, torch.empty)
         dx = torch.empty_like(xc)
         check(L.salun_ln_bf16_backward(_dev(dyc, torch.bfloat16, "dy"), _dev(xc, torch.bfloat16, "x"),
                                        _dev(weight, torch.float32, "gamma"), _dev(stats, torch.float32, "stats"),
-                                       c_void_p(dx.data_ptr()), _dev(gw, torch.float32, "dgamma"),
-                                       _dev(gb, torch.float32, "dbeta"), c_int64(rows), C, int(sunk),
+                                       c_void_p(dx.data_ptr()), _dev(dg.out, torch.float32, "dgamma"),
+                                       _dev(db.out, torch.float32, "dbeta"), c_int64(rows), C, int(dg.accumulate),
                                        c_void_p(ws.data_ptr()), c_size_t(ws.numel()), _stream()), "salun_ln_bf16_backward")
-        return dx, (None if sunk else gw), (None if sunk else gb), None
+        return dx, dg.returned(), db.returned(), None
 
 
 def layer_norm_bf16(x: torch.Tensor, ln: "torch.nn.LayerNorm") -> torch.Tensor:

@@ -26,7 +26,6 @@ import torch.nn as nn
 
 import os
 
-from . import dist as sdist
 from . import draws, gradsink, ops, wgrad_side
 
 FWD_SHORTCUT_BESIDE = os.environ.get("SALUN_FWD_SHORTCUT_BESIDE", "1") != "0"  # _BasicBlockFn.forward
@@ -84,30 +83,11 @@ class _BasicBlockFn(FastFunction):
         grads = {}
 
         def bn_bwd(dy, y, xin, g, b, m, i, relu, want_dres):
-            gw, gb = gradsink.sink(g), gradsink.sink(b)
-            if gw is None or gb is None:
-                gw = gb = None
-            dx, dres, dg, db = ops.bn_backward(dy, y, xin, g, m, i, training, relu, want_dres, gw, gb)
-            if gw is not None:
-                gradsink.arrived(g)
-                gradsink.arrived(b)
-                dg = db = None
-            return dx, dres, dg, db
+            to_g, to_b = gradsink.pair(g, b)
+            dx, dres, dg, db = ops.bn_backward(dy, y, xin, g, m, i, training, relu, want_dres, to_g.out, to_b.out)
+            return dx, dres, to_g.returned(dg), to_b.returned(db)
 
-        dev = dout.device
-        overlap = wgrad_side.OVERLAP
-
-        def wgrad(xin, dy, w, stride, pad):
-            dst = gradsink.sink(w)
-            if overlap:
-                dw = wgrad_side.beside(dev, (xin, dy), lambda side: ops.conv2d_backward_weight(
-                    xin, dy, w.shape, stride, pad, out=dst, accumulate=True, shared=True, stream=side), alloc=dst is None)
-            else:
-                dw = ops.conv2d_backward_weight(xin, dy, w.shape, stride, pad, out=dst, accumulate=True)
-            if dst is not None:
-                gradsink.arrived(w)
-                return None
-            return dw
+        wgrad = wgrad_side.ConvWgrad(dout.device)
 
         # parameters are visited last-to-first so gradient-arrival hooks see the order autograd would produce
         dc2, dskip, dg2, db2 = bn_bwd(dout, out, c2, g2, b2, m2, i2, True, True)
@@ -125,10 +105,7 @@ class _BasicBlockFn(FastFunction):
         dc1, _, dg1, db1 = bn_bwd(dy1, y1, c1, g1, b1, m1, i1, True, False)
         dw1 = wgrad(x, dc1, w1, s, 1)
         dx = ops.conv2d_backward_data(dc1, w1, x.shape, s, 1, addend=dxd) if ctx.needs_input_grad[0] else None
-        if overlap and not all(g is None for g in (dw1, dw2, dwd)):
-            # autograd route: AccumulateGrad consumes the returned tensors on the main stream -> join now
-            torch.cuda.current_stream(dev).wait_stream(wgrad_side.stream(dev))
-            wgrad_side.release_held(dev)
+        wgrad.finish()
         return dx, None, dw1, dg1, db1, dw2, dg2, db2, dwd, dgd, dbd
 
 
@@ -178,16 +155,22 @@ def _structure_ok(blk) -> bool:
     return ok
 
 
-def fused_basic_block(blk, x: torch.Tensor):
-    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4) or torch.is_autocast_enabled():
-        return None
+def _admitted(blk, x: torch.Tensor, structure_ok, probe) -> bool:
+    """The block's structure fits the node (checked per call: modules can be edited) and every launch of the node was
+    probed for this input — once per (shape, device)."""
     cache = blk.__dict__.setdefault("_fused_shapes", {})
     key = (tuple(x.shape), x.device)
     ok = cache.get(key)
     if ok is None:
         with torch.no_grad():
-            ok = cache[key] = _structure_ok(blk) and _probe(blk, tuple(x.shape), x.device)
-    if not ok or not _structure_ok(blk):
+            ok = cache[key] = structure_ok(blk) and probe(blk, tuple(x.shape), x.device)
+    return ok and structure_ok(blk)
+
+
+def fused_basic_block(blk, x: torch.Tensor):
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4) or torch.is_autocast_enabled():
+        return None
+    if not _admitted(blk, x, _structure_ok, _probe):
         return None
     x = x.contiguous()
     d = blk.downsample
@@ -239,77 +222,46 @@ class _DiffusionResnetBlockFn(FastFunction):
         x, a1, c1, a2, n1w, n1b, w1, b1, n2w, n2b, w2, b2, ws, bs, m1, r1, m2, r2 = ctx.saved_tensors
         G1, G2, p, dkey = ctx.cfg
         dout = dout.contiguous()
-        dev = dout.device
-        overlap = wgrad_side.OVERLAP
-        returned = []  # weight gradients handed back to autograd (no sink): they need the main stream to have joined
-
-        def wgrad(xin, dy, w, pad):
-            dst = gradsink.sink(w)
-            if overlap:
-                dw = wgrad_side.beside(dev, (xin, dy), lambda side: ops.conv2d_backward_weight(
-                    xin, dy, w.shape, 1, pad, out=dst, accumulate=True, shared=True, stream=side), alloc=dst is None)
-            else:
-                dw = ops.conv2d_backward_weight(xin, dy, w.shape, 1, pad, out=dst, accumulate=True)
-            if dst is not None:
-                gradsink.arrived(w)
-                return None
-            returned.append(dw)
-            return dw
-
-        def gn_sinks(g, b):
-            gw, gb = gradsink.sink(g), gradsink.sink(b)
-            return (gw, gb) if gw is not None and gb is not None else (None, None)
-
+        wgrad = wgrad_side.ConvWgrad(dout.device)
         # ---- bias gradients of conv2 and of the skip convolution: one channel sum of dout
-        db2 = dbs = None
-        s2, ss = gradsink.sink(b2), (gradsink.sink(bs) if bs is not None else None)
-        if bs is None and s2 is not None:
-            ops.channel_sum(dout, out=s2, accumulate=True)
+        dbs = None
+        to_b2 = gradsink.dest(b2)
+        if bs is None:
+            db2 = to_b2.returned(ops.channel_sum(dout, out=to_b2.out, accumulate=to_b2.accumulate))
         else:
             csum = ops.channel_sum(dout)
-            if s2 is not None:
-                s2.add_(csum)
-            else:
-                db2 = csum
-            if bs is not None:
-                if ss is not None:
-                    ss.add_(csum)
-                else:
-                    # never hand ONE tensor to autograd as the gradient of two parameters: AccumulateGrad may adopt it
-                    # as `.grad` without a copy, and the two `.grad`s would alias
-                    dbs = csum.clone() if db2 is csum else csum
+            db2, dbs = to_b2.add(csum), gradsink.dest(bs).add(csum)
+            if dbs is db2 is csum:
+                # never hand ONE tensor to autograd as the gradient of two parameters: AccumulateGrad may adopt it
+                # as `.grad` without a copy, and the two `.grad`s would alias
+                dbs = csum.clone()
         # ---- conv2
-        dw2 = wgrad(a2, dout, w2, 1)
+        dw2 = wgrad(a2, dout, w2, 1, 1)
         da2 = ops.conv2d_backward_data(dout, w2, a2.shape, 1, 1)
         if dkey is not None:
             da2 = ops.dropout(da2, p, dkey[0], dkey[1], out=da2)
         # ---- norm2 (+ SiLU): dx = dc1; its per-(image, channel) sums are dproj, their batch sum conv1's bias gradient
-        gw, gb = gn_sinks(n2w, n2b)
-        s1 = gradsink.sink(b1)
-        dc1, dg2, dbt2, nk, cs = ops.gn_backward(da2, c1, n2w, n2b, m2, r2, G2, True, gw, gb, nk_sum=True,
-                                                 csum=s1 is None, csum_acc=s1)
-        if gw is not None:
-            dg2 = dbt2 = None
-        db1 = cs  # None when it was added into b1.grad by the kernel
+        to_g, to_b = gradsink.pair(n2w, n2b)
+        to_b1 = gradsink.dest(b1)
+        dc1, dg2, dbt2, nk, cs = ops.gn_backward(da2, c1, n2w, n2b, m2, r2, G2, True, to_g.out, to_b.out, nk_sum=True,
+                                                 csum=not to_b1.accumulate, csum_acc=to_b1.out)
+        dg2, dbt2, db1 = to_g.returned(dg2), to_b.returned(dbt2), to_b1.returned(cs)
         dproj = nk if ctx.needs_input_grad[1] else None
         # ---- conv1
-        dw1 = wgrad(a1, dc1, w1, 1)
+        dw1 = wgrad(a1, dc1, w1, 1, 1)
         da1 = ops.conv2d_backward_data(dc1, w1, a1.shape, 1, 1)
         # ---- norm1 (+ SiLU) and the skip branch
-        gw, gb = gn_sinks(n1w, n1b)
+        to_g, to_b = gradsink.pair(n1w, n1b)
         dws = None
         if ws is None:
-            dx, dg1, dbt1 = ops.gn_backward(da1, x, n1w, n1b, m1, r1, G1, True, gw, gb, addend=dout)
+            dx, dg1, dbt1 = ops.gn_backward(da1, x, n1w, n1b, m1, r1, G1, True, to_g.out, to_b.out, addend=dout)
         else:
             pad = (ws.shape[2] - 1) // 2
-            dws = wgrad(x, dout, ws, pad)
-            dxg, dg1, dbt1 = ops.gn_backward(da1, x, n1w, n1b, m1, r1, G1, True, gw, gb)
+            dws = wgrad(x, dout, ws, 1, pad)
+            dxg, dg1, dbt1 = ops.gn_backward(da1, x, n1w, n1b, m1, r1, G1, True, to_g.out, to_b.out)
             dx = ops.conv2d_backward_data(dout, ws, x.shape, 1, pad, addend=dxg)
-        if gw is not None:
-            dg1 = dbt1 = None
-        if overlap and returned:
-            torch.cuda.current_stream(dev).wait_stream(wgrad_side.stream(dev))
-            wgrad_side.release_held(dev)
+        dg1, dbt1 = to_g.returned(dg1), to_b.returned(dbt1)
+        wgrad.finish()
         if not ctx.needs_input_grad[0]:
             dx = None
         return dx, dproj, None, dg1, dbt1, dw1, db1, dg2, dbt2, dw2, db2, dws, dbs
@@ -371,13 +323,7 @@ def fused_diffusion_resnet_block(blk, x: torch.Tensor, emb_act: torch.Tensor, pr
     from . import norm
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4) or torch.is_autocast_enabled() or not norm._FUSED_GN:
         return None
-    cache = blk.__dict__.setdefault("_fused_shapes", {})
-    key = (tuple(x.shape), x.device)
-    ok = cache.get(key)
-    if ok is None:
-        with torch.no_grad():
-            ok = cache[key] = _diffusion_block_structure_ok(blk) and _diffusion_block_probe(blk, tuple(x.shape), x.device)
-    if not ok or not _diffusion_block_structure_ok(blk):
+    if not _admitted(blk, x, _diffusion_block_structure_ok, _diffusion_block_probe):
         return None
     if proj is None:
         proj = blk.temb_cemb_proj(emb_act)

@@ -12,6 +12,10 @@ launch (resblock.py, conv.py, conv_bf16.py) goes through `beside()`, which
   4. keeps autograd from accumulating into dy in place meanwhile (`hold_until_join`);
   5. queues one join of the main stream behind the side stream at the end of the backward pass.
 
+The policy around it — where the gradient goes, whether the launch runs beside backward-data, when the node must join the
+streams itself — is `ConvWgrad` for the nodes that walk several fp32 convolutions by hand (resblock.py); the single-layer
+nodes (conv._ConvFn, conv_bf16._weight_bias_grad) overlap only what lands in `.grad` and never join.
+
 Under data parallel a gradient slice's all-reduce waits for the side stream itself (dist.BucketedGradReducer).
 SALUN_WGRAD_OVERLAP=0 keeps everything on one stream.  `overlap_disabled()` rebinds `OVERLAP`: read it as
 `wgrad_side.OVERLAP`, never through `from ... import`.
@@ -23,7 +27,7 @@ from typing import Optional
 
 import torch
 
-from . import streams
+from . import gradsink, ops, streams
 
 OVERLAP = os.environ.get("SALUN_WGRAD_OVERLAP", "1") != "0"
 
@@ -145,3 +149,34 @@ def beside(device: torch.device, reads, launch, alloc: bool = False):
         hold_until_join(reads[-1])
         _join_at_end_of_backward(device)
     return out
+
+
+class ConvWgrad:
+    """The weight gradients of the fp32 convolutions of ONE backward node that walks several layers by hand
+    (resblock.py): `wgrad(xin, dy, w, stride, pad)` per convolution, `wgrad.finish()` before the node returns.
+    Each gradient goes where gradsink.dest(w) says; the launch runs beside backward-data whenever `OVERLAP` (read once
+    per node), else on the main stream.  A gradient that goes back to autograd from the side stream is consumed by
+    AccumulateGrad on the main stream as soon as the node returns, so `finish()` joins the streams then — and only then:
+    gradients added into `.grad` wait for the end-of-backward join."""
+    __slots__ = ("device", "overlap", "join")
+
+    def __init__(self, device: torch.device):
+        self.device, self.overlap, self.join = device, OVERLAP, False
+
+    def __call__(self, xin, dy, w, stride: int, pad: int):
+        d = gradsink.dest(w)
+        if self.overlap:
+            dw = beside(self.device, (xin, dy), lambda side: ops.conv2d_backward_weight(
+                xin, dy, w.shape, stride, pad, out=d.out, accumulate=d.accumulate, shared=True, stream=side),
+                alloc=not d.accumulate)
+        else:
+            dw = ops.conv2d_backward_weight(xin, dy, w.shape, stride, pad, out=d.out, accumulate=d.accumulate)
+        dw = d.returned(dw)
+        if dw is not None:
+            self.join = self.overlap
+        return dw
+
+    def finish(self) -> None:
+        if self.join:
+            torch.cuda.current_stream(self.device).wait_stream(stream(self.device))
+            release_held(self.device)

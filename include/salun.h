@@ -978,6 +978,40 @@ int salun_maxpool2x2_forward(const float *x /*dev*/, float *y /*dev, NC*H/2*W/2*
 int salun_maxpool2x2_backward(const float *dy /*dev*/, const uint8_t *idx /*dev*/, float *dx /*dev, NC*H*W*/,
                               int64_t NC, int H, int W, salun_stream_t stream);
 
+/* ----------------------------------------------------------------- K25 --
+ * RBF C-SVC fit and predict for the membership-inference attack (csrc/salun_svc.hip).
+ * Replaces  sklearn.svm.SVC(C=3, gamma='auto', kernel='rbf').fit / .predict  Classification/evaluation/SVC_MIA.py:53-82.
+ * The problem is libsvm's C-SVC dual (Fan, Chen, Lin 2005):  min 1/2 a'Qa - e'a,  0 <= a_t <= C,  y'a = 0,
+ *   Q_ts = y_t y_s K_ts,  K_ts = exp(-gamma |x_t - x_s|^2),  y_t = +1 where y01[t] != 0 (member), -1 otherwise,
+ *   f(z) = sum_t a_t y_t K(x_t, z) - rho,  member iff f(z) > 0.
+ * X [n, d] fp32 row-major, 2 <= n <= SALUN_SVC_MAX_N, 1 <= d <= SALUN_SVC_MAX_D.
+ * ws (salun_svc_rbf_workspace_bytes(n), 0 outside the limits): K [n, n] fp32, then the solver's gradient and state.
+ * salun_svc_rbf_gram: K_ts into ws, all CUs.  The squared distance is summed over the features in index order in
+ *   fp64, multiplied by -gamma, exp in fp64, and the entry rounded ONCE to fp32 (libsvm's Qfloat).
+ * salun_svc_rbf_fit: SMO on the K that salun_svc_rbf_gram left in ws (same ws, same n): second-order working-set
+ *   selection (WSS 2), no shrinking; alpha, gradient and rho in fp64; ties in either selection go to the lowest
+ *   index; a curvature <= 0 is replaced by 1e-12; libsvm's clipped two-variable update (a clipped value IS 0 or C);
+ *   stops when m(alpha) - M(alpha) < eps or after max_iter updates; rho = mean of y_t G_t over free variables, else the
+ *   midpoint of the bounds.  ONE launch of ONE workgroup runs the whole loop: no grid barrier, no cross-workgroup
+ *   flag, no spin; the loop is bounded by max_iter.  Writes alpha[n], *rho and status[0] = updates made,
+ *   status[1] = 1 if the stopping rule was met, 0 if max_iter ended the loop (alpha is feasible either way).
+ *   Deterministic: the same inputs give the same bits.
+ * salun_svc_rbf_decision: dec[q] = sum_t coef[t] K(x_t, z_q) - *rho in fp64 over the entries with coef[t] != 0
+ *   (coef[t] = alpha_t y_t), fixed summation order, and pred[q] = (dec[q] > 0).  dec or pred may be NULL.  All CUs.
+ * SALUN_EINVAL: n, d or m outside the limits, a NULL required pointer, C <= 0, eps <= 0, gamma <= 0 or not finite,
+ *   max_iter < 0.  SALUN_ENOSPC: ws_bytes short of the query. */
+#define SALUN_SVC_MAX_N 65536
+#define SALUN_SVC_MAX_D 16
+size_t salun_svc_rbf_workspace_bytes(int64_t n);
+int salun_svc_rbf_gram(const float *X /*dev, n*d*/, int64_t n, int d, double gamma, void *ws /*dev*/, size_t ws_bytes,
+                       salun_stream_t stream);
+int salun_svc_rbf_fit(const uint8_t *y01 /*dev, n*/, int64_t n, double C, double eps, int64_t max_iter,
+                      double *alpha /*dev, n*/, double *rho /*dev, 1*/, int64_t *status /*dev, 2*/, void *ws /*dev*/,
+                      size_t ws_bytes, salun_stream_t stream);
+int salun_svc_rbf_decision(const float *X /*dev, n*d*/, const double *coef /*dev, n*/, const double *rho /*dev, 1*/,
+                           int64_t n, int d, double gamma, const float *Z /*dev, m*d*/, int64_t m,
+                           double *dec /*dev, m, or NULL*/, uint8_t *pred /*dev, m, or NULL*/, salun_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -101,7 +101,20 @@ def run(argv=None, use_mask: bool = True):
 
     for deprecated in ("MIA", "SVC_MIA", "SVC_MIA_forget"):
         evaluation_result.pop(deprecated, None)
-    if "SVC_MIA_forget_efficacy" not in evaluation_result:
+    backend = arg_parser.mia_backend(args)
+    if "SVC_MIA_forget_efficacy" not in evaluation_result and backend == "device":
+        # probabilities, features, fit and predict on the device (K25); sklearn is not imported
+        from .evaluation import SVC_MIA
+        test_len = len(test_loader.dataset)
+        utils.dataset_convert_to_test(retain_dataset, args)
+        utils.dataset_convert_to_test(forget_dataset, args)
+        utils.dataset_convert_to_test(test_loader.dataset, args)
+        mia_loader = lambda d: BatchLoader(d, args.batch_size, False, device_resident=bool(args.device_loader),
+                                           device=device)
+        evaluation_result["SVC_MIA_forget_efficacy"] = SVC_MIA(
+            shadow_train=mia_loader(_head(retain_dataset, test_len)), shadow_test=mia_loader(test_loader.dataset),
+            target_train=None, target_test=mia_loader(forget_dataset), model=model, backend="device")
+    elif "SVC_MIA_forget_efficacy" not in evaluation_result:
         try:
             from .evaluation import SVC_MIA
         except Exception as e:  # sklearn missing

@@ -74,7 +74,15 @@ _BUILD_FLAGS = [
                             help="use the library (MIOpen) convolutions instead of the fp32 MFMA kernels")),
     ("--thresholds", dict(type=str, default=None,
                           help="comma list of mask ratios for generate_mask (default: the reference's 0.1..1.0)")),
+    # default=SUPPRESS: the namespace carries `mia` only when the flag is given, so the set of defaults stays the one
+    # tests/test_cli.py pins; readers use mia_backend(args)
+    ("--mia", dict(choices=("sklearn", "device"), default=argparse.SUPPRESS,
+                   help="SVC_MIA backend: sklearn on the host (default) or the RBF-SVC kernels on the device (K25)")),
 ]
+
+
+def mia_backend(args) -> str:
+    return getattr(args, "mia", "sklearn")
 
 
 def build_parser() -> argparse.ArgumentParser:

@@ -65,6 +65,8 @@ SALUN_GEMM_MAX_JOBS = 32
 SALUN_GEMM_MAX_SEGS = 32
 SALUN_CLS_HEAD_MAX_C = 8192
 SALUN_CLS_HEAD_MAX_K = 1024
+SALUN_SVC_MAX_N = 65536
+SALUN_SVC_MAX_D = 16
 
 # name -> (restype, argtypes); mirrors include/salun.h one to one
 # (tests/test_cabi.py checks this table against the header and the .so).
@@ -221,6 +223,12 @@ SIGNATURES = {
     "salun_cls_head_backward": (c_int, [c_void_p] * 9 + [c_int, c_int, c_int64, c_int, c_int, c_int, c_void_p]),
     "salun_maxpool2x2_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "salun_maxpool2x2_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    "salun_svc_rbf_workspace_bytes": (c_size_t, [c_int64]),
+    "salun_svc_rbf_gram": (c_int, [c_void_p, c_int64, c_int, c_double, c_void_p, c_size_t, c_void_p]),
+    "salun_svc_rbf_fit": (c_int, [c_void_p, c_int64, c_double, c_double, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_size_t, c_void_p]),
+    "salun_svc_rbf_decision": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_double, c_void_p, c_int64, c_void_p,
+                                       c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -999,9 +999,14 @@ int salun_maxpool2x2_backward(const float *dy /*dev*/, const uint8_t *idx /*dev*
  * salun_svc_rbf_decision: dec[q] = sum_t coef[t] K(x_t, z_q) - *rho in fp64 over the entries with coef[t] != 0
  *   (coef[t] = alpha_t y_t), fixed summation order, and pred[q] = (dec[q] > 0).  dec or pred may be NULL.  All CUs.
  * SALUN_EINVAL: n, d or m outside the limits, a NULL required pointer, C <= 0, eps <= 0, gamma <= 0 or not finite,
- *   max_iter < 0.  SALUN_ENOSPC: ws_bytes short of the query. */
+ *   max_iter < 0.  SALUN_ENOSPC: ws_bytes short of the query.
+ * salun_svc_rbf_gram_wide / salun_svc_rbf_decision_wide: the same contracts for 1 <= d <= SALUN_SVC_WIDE_MAX_D (the
+ *   attack's probability-vector feature has one entry per class: 100 for CIFAR-100, 200 for Tiny-ImageNet).  The
+ *   feature rows and the query point pass through LDS instead of registers; the arithmetic and its order are those
+ *   of the narrow pair, so for d <= SALUN_SVC_MAX_D the results are the same bits.  salun_svc_rbf_fit serves both. */
 #define SALUN_SVC_MAX_N 65536
 #define SALUN_SVC_MAX_D 16
+#define SALUN_SVC_WIDE_MAX_D 1024
 size_t salun_svc_rbf_workspace_bytes(int64_t n);
 int salun_svc_rbf_gram(const float *X /*dev, n*d*/, int64_t n, int d, double gamma, void *ws /*dev*/, size_t ws_bytes,
                        salun_stream_t stream);
@@ -1011,6 +1016,12 @@ int salun_svc_rbf_fit(const uint8_t *y01 /*dev, n*/, int64_t n, double C, double
 int salun_svc_rbf_decision(const float *X /*dev, n*d*/, const double *coef /*dev, n*/, const double *rho /*dev, 1*/,
                            int64_t n, int d, double gamma, const float *Z /*dev, m*d*/, int64_t m,
                            double *dec /*dev, m, or NULL*/, uint8_t *pred /*dev, m, or NULL*/, salun_stream_t stream);
+int salun_svc_rbf_gram_wide(const float *X /*dev, n*d*/, int64_t n, int d, double gamma, void *ws /*dev*/,
+                            size_t ws_bytes, salun_stream_t stream);
+int salun_svc_rbf_decision_wide(const float *X /*dev, n*d*/, const double *coef /*dev, n*/,
+                                const double *rho /*dev, 1*/, int64_t n, int d, double gamma,
+                                const float *Z /*dev, m*d*/, int64_t m, double *dec /*dev, m, or NULL*/,
+                                uint8_t *pred /*dev, m, or NULL*/, salun_stream_t stream);
 
 #ifdef __cplusplus
 }

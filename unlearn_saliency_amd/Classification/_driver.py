@@ -18,7 +18,8 @@ from .dataset import BatchLoader, split_marked
 from .trainer import validate
 
 
-def run(argv=None, use_mask: bool = True):
+def run(argv=None, use_mask: bool = True, synthetic_sizes=None):
+    """`synthetic_sizes` = (n_train, n_test) shrinks the synthetic stand-in of the datasets that take one (tests)."""
     args = arg_parser.parse_args(argv)
     rk, lrk, ws = sdist.init_from_env()
     if not torch.cuda.is_available():
@@ -30,7 +31,7 @@ def run(argv=None, use_mask: bool = True):
     if args.seed:
         utils.setup_seed(args.seed)
     seed = args.seed
-    model, train_loader_full, val_loader, test_loader, marked_loader = utils.setup_model_dataset(args)
+    model, train_loader_full, val_loader, test_loader, marked_loader = utils.setup_model_dataset(args, synthetic_sizes)
     model.to(device)
     if not args.library_conv:
         from ..conv import use_salun_convs

@@ -67,7 +67,8 @@ def _svc_acc_device(shadow_in, shadow_out, target_in, target_out, stages=None):
     m_in, m_out = len(target_in), len(target_out)
     if m_in + m_out == 0:
         raise ValueError("SVC_MIA: no target points")
-    model = ops_svc.fit(X, y, C=SVC_C, eps=SVC_TOL, wait=False, stages=stages)
+    # the probability-vector feature has one entry per class: past K25's register-resident limit it takes the wide pair
+    model = ops_svc.fit(X, y, C=SVC_C, eps=SVC_TOL, wait=False, stages=stages, wide=d > ops_svc.max_features(False))
     _, pred = ops_svc.decision(model, Q, stages=stages)
     p = pred.double()
     zero = torch.zeros((), dtype=torch.float64, device=dev)

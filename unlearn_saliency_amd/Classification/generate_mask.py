@@ -101,7 +101,7 @@ def save_gradient_ratio(data_loaders, model, criterion, args):
     return flat_masks
 
 
-def main(argv=None):
+def main(argv=None, synthetic_sizes=None):
     args = arg_parser.parse_args(argv)
     rk, lrk, ws = sdist.init_from_env()
     if torch.cuda.is_available():
@@ -114,7 +114,7 @@ def main(argv=None):
     if args.seed:
         utils.setup_seed(args.seed)
     seed = args.seed
-    model, train_loader_full, val_loader, test_loader, marked_loader = utils.setup_model_dataset(args)
+    model, train_loader_full, val_loader, test_loader, marked_loader = utils.setup_model_dataset(args, synthetic_sizes)
     model.to(device)
     if not args.library_conv:
         from ..conv import use_salun_convs

@@ -12,8 +12,8 @@ if __package__ in (None, ""):
 from ._driver import run
 
 
-def main(argv=None):
-    return run(argv, use_mask=True)
+def main(argv=None, synthetic_sizes=None):
+    return run(argv, use_mask=True, synthetic_sizes=synthetic_sizes)
 
 
 if __name__ == "__main__":

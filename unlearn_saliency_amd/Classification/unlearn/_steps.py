@@ -34,7 +34,7 @@ def run_pass(loader, model, criterion, optimizer, epoch: int, args, *,
              losses: Optional[utils.AverageMeter] = None, top1: Optional[utils.AverageMeter] = None,
              loader_len: Optional[int] = None, warmup_steps_per_epoch: Optional[int] = None,
              batch_label_fn: Optional[Callable[[torch.Tensor, torch.Tensor], torch.Tensor]] = None,
-             after_step: Optional[Callable[[int], None]] = None, step_offset: int = 0):
+             after_step: Optional[Callable[[int], None]] = None, step_offset: int = 0, print_offset: int = 0):
     """Run every batch of `loader` through forward/backward/fused-step.
 
     label_fn   maps the batch's true targets (CPU or device) to the targets used in the loss
@@ -44,6 +44,8 @@ def run_pass(loader, model, criterion, optimizer, epoch: int, args, *,
     batch_label_fn  (device image, device true target) -> labels for the loss; accuracy is still measured against
                the TRUE targets (boundary_sh.py:99-116: loss on the adversarial neighbour label, prec1 on `target`).
     after_step      called with the loop index after every optimizer step (RL_proximal's soft-threshold).
+    print_offset    added to the loop index in the progress line and in its `print_freq` test (RL's merged pass counts
+               its batches from len(forget_loader), RL.py:74).
     """
     dev = next(model.parameters()).device
     loader_len = len(loader) if loader_len is None else loader_len
@@ -97,11 +99,11 @@ def run_pass(loader, model, criterion, optimizer, epoch: int, args, *,
                 loss_sum += loss.detach().double() * n
                 hit_sum += (output.detach().argmax(dim=1) == target).sum().double()
             seen += n
-            if (i + 1) % args.print_freq == 0:
+            if (i + print_offset + 1) % args.print_freq == 0:
                 end = time.time()
                 print("Epoch: [{0}][{1}/{2}]\tLoss ({3:.4f})\tAccuracy ({4:.3f})\tTime {5:.2f}".format(
-                    epoch, i, loader_len, float(loss_sum.item()) / seen, float(hit_sum.item()) * 100.0 / seen,
-                    end - start))
+                    epoch, i + print_offset, loader_len, float(loss_sum.item()) / seen,
+                    float(hit_sum.item()) * 100.0 / seen, end - start))
                 start = time.time()
     if track and seen:
         if losses is not None:

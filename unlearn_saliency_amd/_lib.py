@@ -67,6 +67,7 @@ SALUN_CLS_HEAD_MAX_C = 8192
 SALUN_CLS_HEAD_MAX_K = 1024
 SALUN_SVC_MAX_N = 65536
 SALUN_SVC_MAX_D = 16
+SALUN_SVC_WIDE_MAX_D = 1024
 
 # name -> (restype, argtypes); mirrors include/salun.h one to one
 # (tests/test_cabi.py checks this table against the header and the .so).
@@ -229,6 +230,9 @@ SIGNATURES = {
                                   c_size_t, c_void_p]),
     "salun_svc_rbf_decision": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_double, c_void_p, c_int64, c_void_p,
                                        c_void_p, c_void_p]),
+    "salun_svc_rbf_gram_wide": (c_int, [c_void_p, c_int64, c_int, c_double, c_void_p, c_size_t, c_void_p]),
+    "salun_svc_rbf_decision_wide": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_double, c_void_p, c_int64,
+                                            c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -16,6 +16,7 @@
 //                   cooperative launch, no cross-workgroup flag, nothing that spins.  Every loop here is a counted
 //                   `for` over n or is bounded by max_iter.
 //   k_svc_decision  one workgroup per query point, fp64, fixed summation order, all CUs.
+// k_svc_gram_wide / k_svc_decision_wide are the same two for up to SALUN_SVC_WIDE_MAX_D features (below).
 //
 // One iteration of k_svc_fit (all values that steer control flow come out of LDS, so every thread takes the same path):
 //   pass 1  G += Q_i da_i, then += Q_j da_j (the previous update; skipped before the first), and in the same sweep
@@ -293,6 +294,83 @@ __global__ __launch_bounds__(SALUN_BLOCK) void k_svc_decision(const float *__res
   }
 }
 
+// ---- wide features (d up to SALUN_SVC_WIDE_MAX_D): the probability-vector feature of a 100- / 200-class model.
+// Same arithmetic, in the same order, as the two kernels above: for d <= SALUN_SVC_MAX_D the results are the same bits.
+constexpr int GW_KC = 32;             // features per LDS tile
+constexpr int GW_LD = GW_KC + 1;      // tile row stride in floats: lane r reads bank (r * 33 + c) % 32, all distinct
+
+// One work item = row t of K against SALUN_BLOCK consecutive columns s.  x_t sits in LDS as doubles (read as a
+// broadcast); the SALUN_BLOCK rows x_s pass through LDS in tiles of GW_KC features, loaded coalesced (GW_KC consecutive
+// floats of a row per 32 lanes) and read back one row per lane.  Without the tile every lane walks its own row of
+// d floats in global memory, d * 4 bytes apart from its neighbour's.
+__global__ __launch_bounds__(SALUN_BLOCK) void k_svc_gram_wide(const float *__restrict__ X, float *__restrict__ K, int n,
+                                                               int d, double gamma) {
+  __shared__ double s_xt[SALUN_SVC_WIDE_MAX_D];
+  __shared__ float s_tile[SALUN_BLOCK * GW_LD];
+  const int chunks = (n + SALUN_BLOCK - 1) / SALUN_BLOCK;
+  const int64_t items = static_cast<int64_t>(n) * chunks;
+  for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+    const int t = static_cast<int>(item / chunks);
+    const int s0 = static_cast<int>(item - static_cast<int64_t>(t) * chunks) * SALUN_BLOCK;
+    const int rows = min(SALUN_BLOCK, n - s0);
+    __syncthreads();  // the previous item's reads of s_xt and s_tile are done
+    for (int k = threadIdx.x; k < d; k += SALUN_BLOCK) s_xt[k] = static_cast<double>(X[static_cast<int64_t>(t) * d + k]);
+    double acc = 0.0;
+    for (int k0 = 0; k0 < d; k0 += GW_KC) {
+      const int kc = min(GW_KC, d - k0);
+      if (k0) __syncthreads();  // the previous tile has been read
+      for (int e = threadIdx.x; e < SALUN_BLOCK * GW_KC; e += SALUN_BLOCK) {
+        const int r = e / GW_KC, c = e - r * GW_KC;
+        if (r < rows && c < kc) s_tile[r * GW_LD + c] = X[static_cast<int64_t>(s0 + r) * d + k0 + c];
+      }
+      __syncthreads();
+      if (static_cast<int>(threadIdx.x) < rows) {
+        const float *row = s_tile + threadIdx.x * GW_LD;
+        for (int c = 0; c < kc; ++c) {
+          const double df = s_xt[k0 + c] - static_cast<double>(row[c]);
+          acc = acc + df * df;
+        }
+      }
+    }
+    if (static_cast<int>(threadIdx.x) < rows)
+      K[static_cast<int64_t>(t) * n + s0 + threadIdx.x] = static_cast<float>(exp(-gamma * acc));
+  }
+}
+
+// k_svc_decision with the query point in LDS instead of SALUN_SVC_MAX_D registers; one workgroup per query point.
+__global__ __launch_bounds__(SALUN_BLOCK) void k_svc_decision_wide(const float *__restrict__ X,
+                                                                   const double *__restrict__ coef,
+                                                                   const double *__restrict__ rho, int n, int d,
+                                                                   double gamma, const float *__restrict__ Z, int64_t m,
+                                                                   double *__restrict__ dec, uint8_t *__restrict__ pred) {
+  __shared__ double lds[4];
+  __shared__ double s_z[SALUN_SVC_WIDE_MAX_D];
+  for (int64_t q = blockIdx.x; q < m; q += gridDim.x) {
+    __syncthreads();  // the previous query's reads of s_z are done
+    for (int k = threadIdx.x; k < d; k += SALUN_BLOCK) s_z[k] = static_cast<double>(Z[q * d + k]);
+    __syncthreads();
+    double part = 0.0;
+    for (int t = threadIdx.x; t < n; t += SALUN_BLOCK) {
+      const double c = coef[t];
+      if (c != 0.0) {
+        const float *xt = X + static_cast<int64_t>(t) * d;
+        double acc = 0.0;
+        for (int k = 0; k < d; ++k) {
+          const double df = static_cast<double>(xt[k]) - s_z[k];
+          acc = acc + df * df;
+        }
+        part = part + c * exp(-gamma * acc);
+      }
+    }
+    const double total = salun_block_sum(part, lds);
+    if (threadIdx.x == 0) {
+      const double f = total - *rho;
+      if (dec) dec[q] = f;
+      if (pred) pred[q] = f > 0.0 ? 1 : 0;
+    }
+  }
+}
+
 size_t align16(size_t b) { return (b + 15u) & ~static_cast<size_t>(15u); }
 bool n_ok(int64_t n) { return n >= 2 && n <= SALUN_SVC_MAX_N; }
 bool positive_finite(double v) { return v > 0.0 && v <= 1.7976931348623157e308; }
@@ -346,6 +424,33 @@ SALUN_EXPORT int salun_svc_rbf_decision(const float *X, const double *coef, cons
     return SALUN_EINVAL;
   hipLaunchKernelGGL(k_svc_decision, dim3(salun_grid_for(m, 1)), dim3(SALUN_BLOCK), 0, salun_hip_stream(stream), X, coef,
                      rho, static_cast<int>(n), d, gamma, Z, m, dec, pred);
+  SALUN_LAUNCH_CHECK();
+  return SALUN_OK;
+}
+
+SALUN_EXPORT int salun_svc_rbf_gram_wide(const float *X, int64_t n, int d, double gamma, void *ws, size_t ws_bytes,
+                                         salun_stream_t stream) {
+  if (!n_ok(n) || d < 1 || d > SALUN_SVC_WIDE_MAX_D || !X || !ws || !positive_finite(gamma)) return SALUN_EINVAL;
+  if (!salun_aligned4(X) || !salun_aligned16(ws)) return SALUN_EINVAL;
+  if (ws_bytes < salun_svc_rbf_workspace_bytes(n)) return SALUN_ENOSPC;
+  const int64_t items = n * ((n + SALUN_BLOCK - 1) / SALUN_BLOCK);
+  hipLaunchKernelGGL(k_svc_gram_wide, dim3(salun_grid_for(items, 1)), dim3(SALUN_BLOCK), 0, salun_hip_stream(stream), X,
+                     static_cast<float *>(ws), static_cast<int>(n), d, gamma);
+  SALUN_LAUNCH_CHECK();
+  return SALUN_OK;
+}
+
+SALUN_EXPORT int salun_svc_rbf_decision_wide(const float *X, const double *coef, const double *rho, int64_t n, int d,
+                                             double gamma, const float *Z, int64_t m, double *dec, uint8_t *pred,
+                                             salun_stream_t stream) {
+  if (n < 1 || n > SALUN_SVC_MAX_N || d < 1 || d > SALUN_SVC_WIDE_MAX_D || m < 1 || m > (int64_t(1) << 40))
+    return SALUN_EINVAL;
+  if (!X || !coef || !rho || !Z || (!dec && !pred) || !positive_finite(gamma)) return SALUN_EINVAL;
+  if (!salun_aligned4(X) || !salun_aligned4(Z) || (reinterpret_cast<uintptr_t>(coef) & 7u) ||
+      (reinterpret_cast<uintptr_t>(rho) & 7u) || (reinterpret_cast<uintptr_t>(dec) & 7u))
+    return SALUN_EINVAL;
+  hipLaunchKernelGGL(k_svc_decision_wide, dim3(salun_grid_for(m, 1)), dim3(SALUN_BLOCK), 0, salun_hip_stream(stream), X,
+                     coef, rho, static_cast<int>(n), d, gamma, Z, m, dec, pred);
   SALUN_LAUNCH_CHECK();
   return SALUN_OK;
 }

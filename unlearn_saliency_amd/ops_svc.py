@@ -4,6 +4,10 @@ attack, fitted and evaluated on the device.
 Same conventions as ops.py: device tensors only, raw pointers and the current stream handed to libsalun.so, a failing
 call raises `SalunError`.  `fit` is gram -> fit, `decision` evaluates a fitted model; both are stream-ordered.  The
 solver's loop is bounded by `max_iter`; a fit that ends there raises `SvcNotConverged` — reported, never silent.
+
+`wide=True` selects the kernels that take up to SALUN_SVC_WIDE_MAX_D features (the probability vector of a 100- or
+200-class model); the default keeps the register-resident pair and its limit of SALUN_SVC_MAX_D.  A model remembers
+which pair fitted it.
 """
 from __future__ import annotations
 
@@ -52,9 +56,9 @@ class SvcModel:
     """A fitted model: X [n, d] fp32, coef [n] fp64 (alpha_t y_t; 0 off the support set), alpha [n] fp64, rho [1] fp64
     and status [2] int64 (updates made, converged), all on the device."""
 
-    def __init__(self, X, coef, alpha, rho, status, gamma, C, eps, max_iter):
+    def __init__(self, X, coef, alpha, rho, status, gamma, C, eps, max_iter, wide=False):
         self.X, self.coef, self.alpha, self.rho, self.status = X, coef, alpha, rho, status
-        self.gamma, self.C, self.eps, self.max_iter = gamma, C, eps, max_iter
+        self.gamma, self.C, self.eps, self.max_iter, self.wide = gamma, C, eps, max_iter, wide
 
     def raise_unless_converged(self) -> int:
         """One host read of the status; returns the number of updates."""
@@ -68,23 +72,28 @@ def workspace_bytes(n: int) -> int:
     return int(_lib.lib().salun_svc_rbf_workspace_bytes(c_int64(n)))
 
 
-def rbf_gram(X: torch.Tensor, gamma: float, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+def max_features(wide: bool) -> int:
+    return _lib.SALUN_SVC_WIDE_MAX_D if wide else _lib.SALUN_SVC_MAX_D
+
+
+def rbf_gram(X: torch.Tensor, gamma: float, ws: Optional[torch.Tensor] = None, wide: bool = False) -> torch.Tensor:
     """The workspace with K [n, n] fp32 at its start (K = ws[:4 n^2].view(float32).view(n, n))."""
     n, d = X.shape
     nbytes = workspace_bytes(n)
-    if nbytes == 0 or not 1 <= d <= _lib.SALUN_SVC_MAX_D:
+    if nbytes == 0 or not 1 <= d <= max_features(wide):
         raise ValueError(f"RBF-SVC: n = {n}, d = {d} outside 2 <= n <= {_lib.SALUN_SVC_MAX_N}, "
-                         f"1 <= d <= {_lib.SALUN_SVC_MAX_D}")
+                         f"1 <= d <= {max_features(wide)}")
     if ws is None:
         ws = torch.empty(nbytes, dtype=torch.uint8, device=X.device)
-    check(_lib.lib().salun_svc_rbf_gram(_dev(X, torch.float32, "X"), c_int64(n), d, c_double(gamma),
-                                        _dev(ws, torch.uint8, "ws"), c_size_t(ws.numel()), _stream()),
-          "salun_svc_rbf_gram")
+    name = "salun_svc_rbf_gram_wide" if wide else "salun_svc_rbf_gram"
+    check(getattr(_lib.lib(), name)(_dev(X, torch.float32, "X"), c_int64(n), d, c_double(gamma),
+                                    _dev(ws, torch.uint8, "ws"), c_size_t(ws.numel()), _stream()), name)
     return ws
 
 
 def fit(X: torch.Tensor, y: torch.Tensor, C: float = 3.0, gamma: Optional[float] = None, eps: float = 1e-3,
-        max_iter: Optional[int] = None, wait: bool = True, stages: Optional[dict] = None) -> SvcModel:
+        max_iter: Optional[int] = None, wait: bool = True, stages: Optional[dict] = None,
+        wide: bool = False) -> SvcModel:
     """Fit on X [n, d] fp32 and y [n] uint8 (1 = member).  gamma defaults to 1 / d (sklearn's "auto").
 
     wait=True checks the inputs first (non-finite features and an empty class raise ValueError, as sklearn does) and the
@@ -103,7 +112,7 @@ def fit(X: torch.Tensor, y: torch.Tensor, C: float = 3.0, gamma: Optional[float]
     gamma = 1.0 / d if gamma is None else float(gamma)
     max_iter = default_max_iter(n) if max_iter is None else int(max_iter)
     with _Stage(stages, "gram"):
-        ws = rbf_gram(X, gamma)
+        ws = rbf_gram(X, gamma, wide=wide)
     alpha = torch.empty(n, dtype=torch.float64, device=X.device)
     rho = torch.empty(1, dtype=torch.float64, device=X.device)
     status = torch.empty(2, dtype=torch.int64, device=X.device)
@@ -113,13 +122,14 @@ def fit(X: torch.Tensor, y: torch.Tensor, C: float = 3.0, gamma: Optional[float]
                                            c_void_p(status.data_ptr()), c_void_p(ws.data_ptr()), c_size_t(ws.numel()),
                                            _stream()), "salun_svc_rbf_fit")
     coef = torch.where(y != 0, alpha, -alpha)
-    model = SvcModel(X, coef, alpha, rho, status, gamma, float(C), float(eps), max_iter)
+    model = SvcModel(X, coef, alpha, rho, status, gamma, float(C), float(eps), max_iter, wide)
     if wait:
         model.raise_unless_converged()
     return model
 
 
-def decision_values(X: torch.Tensor, coef: torch.Tensor, rho: torch.Tensor, gamma: float, Z: torch.Tensor):
+def decision_values(X: torch.Tensor, coef: torch.Tensor, rho: torch.Tensor, gamma: float, Z: torch.Tensor,
+                    wide: bool = False):
     """(dec [m] fp64, pred [m] uint8) of Z [m, d] fp32: dec = sum_t coef_t K(x_t, z) - rho, pred = dec > 0."""
     n, d = X.shape
     m = Z.shape[0]
@@ -127,13 +137,14 @@ def decision_values(X: torch.Tensor, coef: torch.Tensor, rho: torch.Tensor, gamm
         raise ValueError(f"RBF-SVC decision: X {tuple(X.shape)}, coef {tuple(coef.shape)}, Z {tuple(Z.shape)}")
     dec = torch.empty(m, dtype=torch.float64, device=X.device)
     pred = torch.empty(m, dtype=torch.uint8, device=X.device)
-    check(_lib.lib().salun_svc_rbf_decision(_dev(X, torch.float32, "X"), _dev(coef, torch.float64, "coef"),
-                                            _dev(rho, torch.float64, "rho"), c_int64(n), d, c_double(gamma),
-                                            _dev(Z, torch.float32, "Z"), c_int64(m), c_void_p(dec.data_ptr()),
-                                            c_void_p(pred.data_ptr()), _stream()), "salun_svc_rbf_decision")
+    name = "salun_svc_rbf_decision_wide" if wide else "salun_svc_rbf_decision"
+    check(getattr(_lib.lib(), name)(_dev(X, torch.float32, "X"), _dev(coef, torch.float64, "coef"),
+                                    _dev(rho, torch.float64, "rho"), c_int64(n), d, c_double(gamma),
+                                    _dev(Z, torch.float32, "Z"), c_int64(m), c_void_p(dec.data_ptr()),
+                                    c_void_p(pred.data_ptr()), _stream()), name)
     return dec, pred
 
 
 def decision(model: SvcModel, Z: torch.Tensor, stages: Optional[dict] = None):
     with _Stage(stages, "decision"):
-        return decision_values(model.X, model.coef, model.rho, model.gamma, Z)
+        return decision_values(model.X, model.coef, model.rho, model.gamma, Z, wide=model.wide)

@@ -1023,6 +1023,34 @@ int salun_svc_rbf_decision_wide(const float *X /*dev, n*d*/, const double *coef 
                                 const float *Z /*dev, m*d*/, int64_t m, double *dec /*dev, m, or NULL*/,
                                 uint8_t *pred /*dev, m, or NULL*/, salun_stream_t stream);
 
+/* ----------------------------------------------------------------- K26 --
+ * Antialiased bilinear resample of uint8 images, bit-identical to Pillow's 8-bit path (csrc/salun_resample.hip;
+ * DESIGN.md §9l).  Replaces  transforms.Resize(config.data.image_size)  DDPM/datasets/__init__.py:36-41, i.e.
+ * PIL.Image.resize((OW, OH), Image.BILINEAR), which the reference runs on the host for every fetch.
+ * src [B, H, W, C] uint8, dst [B, OH, OW, C] uint8, both contiguous, any byte alignment; B >= 1, C in {1, 3, 4},
+ * 1 <= H, W, OH, OW <= SALUN_RESAMPLE_MAX_SIDE.
+ * Per axis (in source samples, out destination samples):  scale = in / out, fs = max(scale, 1), support = 1.0 * fs,
+ *   ss = 1 / fs;  for output index xx:  center = (xx + 0.5) * scale,  xmin = max(0, (int)(center - support + 0.5)),
+ *   xmax = min(in, (int)(center + support + 0.5)),  taps x in [0, xmax - xmin) with
+ *   w = max(0, 1 - |(x + xmin - center + 0.5) * ss|), divided by their sum, then k = (int)(w * 2^22 + 0.5).
+ * An output byte is clip8((2^21 + sum k * pixel) >> 22); the horizontal pass runs first and is rounded to uint8 before
+ * the vertical pass reads it.  The tables are computed on the host in doubles (no contraction to fused multiply-adds),
+ * uploaded once per (device, in, out) pair and kept; the first call for a pair blocks the host for that copy.
+ * ONE launch: a workgroup produces a band of output rows of one image; the horizontal result of the source rows the
+ * band needs lives in LDS and never reaches memory.  salun_resample_u8_lds_bytes is that LDS size for the band height
+ * the launch would use (host arithmetic only), 0 when the arguments are outside the limits or when a band of ONE
+ * output row would need more than SALUN_RESAMPLE_MAX_LDS bytes — such a call is refused, nothing is spilled.
+ * salun_resample_u8_table copies ONE axis's table to HOST memory (no device call; what the tests compare with their
+ * restatement): out first-tap indices, out tap counts, then out rows of *ksize weights (unused tail 0), i.e.
+ * out * (2 + *ksize) int32.  table == NULL only reports *ksize; SALUN_ENOSPC when n_ints is short.
+ * SALUN_EINVAL (nothing is written): any limit above, a NULL pointer, dst == src, a refused size pair. */
+#define SALUN_RESAMPLE_MAX_SIDE 1024
+#define SALUN_RESAMPLE_MAX_LDS 65536
+size_t salun_resample_u8_lds_bytes(int H, int W, int C, int OH, int OW);
+int salun_resample_u8_table(int in, int out, int32_t *table /*host, or NULL*/, size_t n_ints, int *ksize /*host*/);
+int salun_resample_u8(const uint8_t *src /*dev, B*H*W*C*/, uint8_t *dst /*dev, B*OH*OW*C*/, int64_t B, int H, int W,
+                      int C, int OH, int OW, salun_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,8 +1,9 @@
-"""CIFAR-10 loaders for the DDPM runs: the whole training set (`get_dataset`, reference DDPM/datasets/__init__.py:30-77)
+"""CIFAR-10 and STL-10 loaders for the DDPM runs (`config.data.dataset`; STL-10's reader and its one-time device resize
+are in stl10.py): the whole training set (`get_dataset`, reference DDPM/datasets/__init__.py:30-77)
 and the class-split forget / remain sets (reference :120-177, 241-255).  The reference materialises both splits once
 as Python lists of (ToTensor image, label) with the random flip frozen at materialisation time; here both splits are device-resident fp32 tensors built once
 (flip drawn once, like the reference) and batches are index gathers on the GPU.  Falls back to the
-counter-based synthetic CIFAR-shaped set when the dataset files are absent (no network on the GPU box)."""
+counter-based synthetic stand-in of the configured set when the dataset files are absent (no network on the GPU box)."""
 from __future__ import annotations
 
 import numpy as np
@@ -10,10 +11,11 @@ import torch
 
 from ...Classification.dataset import _load_cifar10_files, have_cifar10, synthetic_cifar10
 from ... import dist as sdist
+from . import stl10
 
 
 class TensorLoader:
-    """Shuffling batch iterator over device tensors (x: (N,3,32,32) fp32 in [0,1], c: (N,) int64)."""
+    """Shuffling batch iterator over device tensors (x: (N,3,S,S) fp32 in [0,1], c: (N,) int64)."""
 
     def __init__(self, x, c, batch_size, shuffle=True, rank=0, world_size=1, flip=False):
         self.x, self.c, self.batch_size, self.shuffle = x, c, int(batch_size), shuffle
@@ -49,6 +51,18 @@ def _train_arrays(config, synthetic):
     return x, y
 
 
+def _dataset_name(config) -> str:
+    name = config.data.dataset
+    if name not in ("CIFAR10", "STL10"):
+        raise ValueError(f"data.dataset {name!r}: the DDPM runs read CIFAR10 or STL10")
+    return name
+
+
+def _u8_to_float(xd):
+    """device uint8 NHWC -> fp32 NCHW in [0, 1] (ToTensor)."""
+    return xd.permute(0, 3, 1, 2).float().div_(255).contiguous()
+
+
 def _to_device(x, y, device):
     xt = torch.from_numpy(np.ascontiguousarray(x)).to(device).permute(0, 3, 1, 2).float().div_(255).contiguous()
     return xt, torch.from_numpy(y).to(device)
@@ -58,7 +72,11 @@ def get_dataset(args, config, device=None, synthetic=None):
     """-> loader over the whole training set (`--mode train`): shuffled every pass; with `data.random_flip` each sample
     is mirrored with probability 0.5 every time it is drawn, as the reference's transform does."""
     device = device or torch.device("cuda", torch.cuda.current_device())
-    xt, yt = _to_device(*_train_arrays(config, synthetic), device)
+    if _dataset_name(config) == "STL10":
+        xd, yt = stl10.device_arrays(config, synthetic, device)
+        xt = _u8_to_float(xd)
+    else:
+        xt, yt = _to_device(*_train_arrays(config, synthetic), device)
     return TensorLoader(xt, yt, config.training.batch_size, True, sdist.rank(), sdist.world_size(),
                         flip=bool(getattr(config.data, "random_flip", True)))
 
@@ -66,11 +84,20 @@ def get_dataset(args, config, device=None, synthetic=None):
 def get_forget_dataset(args, config, label_to_drop, device=None, synthetic=None):
     """-> (remain_loader, forget_loader) split by class `label_to_drop`."""
     device = device or torch.device("cuda", torch.cuda.current_device())
-    x, y = _train_arrays(config, synthetic)
-    if getattr(config.data, "random_flip", True):  # frozen once, as in the reference's materialised lists
-        flip = np.random.rand(len(x)) < 0.5
-        x = np.where(flip[:, None, None, None], x[:, :, ::-1, :], x)
-    xt, yt = _to_device(x, y, device)
+    if _dataset_name(config) == "STL10":
+        # resized first (once, on the uint8 originals), mirrored after: the same bytes as the reference's
+        # Resize -> RandomHorizontalFlip, because the resample commutes with a mirror (stl10.py)
+        xd, yt = stl10.device_arrays(config, synthetic, device)
+        if getattr(config.data, "random_flip", True):  # frozen once, as in the reference's materialised lists
+            flip = torch.from_numpy(np.random.rand(len(xd)) < 0.5).to(device)
+            xd = torch.where(flip[:, None, None, None], xd.flip(2), xd)
+        xt = _u8_to_float(xd)
+    else:
+        x, y = _train_arrays(config, synthetic)
+        if getattr(config.data, "random_flip", True):  # frozen once, as in the reference's materialised lists
+            flip = np.random.rand(len(x)) < 0.5
+            x = np.where(flip[:, None, None, None], x[:, :, ::-1, :], x)
+        xt, yt = _to_device(x, y, device)
     forget = yt == int(label_to_drop)
     print(int((~forget).sum()), int(forget.sum()))
     rk, ws = sdist.rank(), sdist.world_size()

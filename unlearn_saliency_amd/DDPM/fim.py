@@ -1,5 +1,6 @@
 """`python fim.py --config cifar10_fim.yml --ckpt_folder F --n_chunks 20` — diagonal Fisher information of the
-ε-MSE objective (reference DDPM/fim.py:14-95 -> Diffusion.save_fim).  Output: {ckpt_folder}/fisher_dict.pkl."""
+ε-MSE objective (reference DDPM/fim.py:14-95 -> Diffusion.save_fim).  Output: {ckpt_folder}/fisher_dict.pkl.
+`--config stl10_fim.yml` for the STL-10 model; the samples are {ckpt_folder}/class_samples either way."""
 import argparse
 import os
 import sys

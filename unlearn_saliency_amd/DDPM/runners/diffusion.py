@@ -6,7 +6,7 @@
     save_fim()          diagonal empirical Fisher                 (reference :101-191)
 
 — same constructor (`Diffusion(args, config)`), same `args` / YAML fields, same artefacts
-(`results/cifar10/mask/{label}/with_0.5.pt` with `module.`-prefixed int64 tensors; `ckpts/ckpt.pth` =
+(`results/cifar10/mask/{label}/with_0.5.pt` — for STL-10 too, the reference hard-codes the folder — with `module.`-prefixed int64 tensors; `ckpts/ckpt.pth` =
 `[model_state, optimizer_state, step]`; `fisher_dict.pkl`).  `sample()` and its modes (reference :621-931) write
 the folders of PNGs the evaluation and `save_fim` / `train_forget` read.  FID stays out of scope
 (SURVEY.md §2 D7).

@@ -1,5 +1,6 @@
 """`python sample.py --config cifar10_sample.yml --ckpt_folder F --mode sample_classes|sample_fid|visualization
 [--n_samples_per_class 500 --classes_to_generate x0 --cond_scale 2.0 --timesteps 1000]`
+(`--config stl10_sample.yml`: the same modes at 64 x 64.)
 
 Same flags and defaults as the reference's DDPM/sample.py:16-75.  Writes the folders of PNGs its evaluation reads —
 `F/class_samples/<class>/<id>.png`, `F/fid_samples_guidance_<s>[_excluded_class_<a>_<b>]/<id>.png`,

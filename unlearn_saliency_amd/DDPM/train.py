@@ -1,6 +1,9 @@
 """`python train.py --config cifar10_saliency_unlearn.yml --ckpt_folder F --label_to_forget 0
 --mode generate_mask|saliency_unlearn [--mask_path M --alpha 1e-3 --method rl]`
 `python train.py --config cifar10_train.yml --mode train` / `--mode retrain --label_to_forget 0`
+The STL-10 runs (64 x 64) take the same commands with `--config stl10_*.yml`; run directories go to
+`results/<data.dataset in lower case>/...`, the mask to `results/cifar10/mask/<label>` for either data set, as the
+reference hard-codes it.
 
 Same flags and the same five modes as the reference's DDPM/train.py:15-93: train (the original model), retrain (every
 class but `--label_to_forget`: the model unlearning is compared against), forget (EWC baseline),
@@ -47,7 +50,7 @@ _FLAGS = [
     ("--mask_ratio", dict(type=float, default=0.5)),
     ("--sparse", dict(type=bool, default=False)),
     # build extensions
-    ("--synthetic", dict(action="store_true", help="random-init U-Net + synthetic CIFAR-shaped data (benchmarks)")),
+    ("--synthetic", dict(action="store_true", help="random-init U-Net + the synthetic stand-in of the config's data set (benchmarks)")),
     ("--n_iters", dict(type=int, default=None, help="override config.training.n_iters")),
     ("--library_conv", dict(action="store_true", help="use the library (MIOpen) convolutions instead of the MFMA kernels")),
 ]

@@ -68,6 +68,8 @@ SALUN_CLS_HEAD_MAX_K = 1024
 SALUN_SVC_MAX_N = 65536
 SALUN_SVC_MAX_D = 16
 SALUN_SVC_WIDE_MAX_D = 1024
+SALUN_RESAMPLE_MAX_SIDE = 1024
+SALUN_RESAMPLE_MAX_LDS = 65536
 
 # name -> (restype, argtypes); mirrors include/salun.h one to one
 # (tests/test_cabi.py checks this table against the header and the .so).
@@ -233,6 +235,9 @@ SIGNATURES = {
     "salun_svc_rbf_gram_wide": (c_int, [c_void_p, c_int64, c_int, c_double, c_void_p, c_size_t, c_void_p]),
     "salun_svc_rbf_decision_wide": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_double, c_void_p, c_int64,
                                             c_void_p, c_void_p, c_void_p]),
+    "salun_resample_u8_lds_bytes": (c_size_t, [c_int] * 5),
+    "salun_resample_u8_table": (c_int, [c_int, c_int, c_void_p, c_size_t, ctypes.POINTER(c_int)]),
+    "salun_resample_u8": (c_int, [c_void_p, c_void_p, c_int64] + [c_int] * 5 + [c_void_p]),
 }
 
 _lib = None

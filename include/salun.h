@@ -1051,6 +1051,84 @@ int salun_resample_u8_table(int in, int out, int32_t *table /*host, or NULL*/, s
 int salun_resample_u8(const uint8_t *src /*dev, B*H*W*C*/, uint8_t *dst /*dev, B*OH*OW*C*/, int64_t B, int H, int W,
                       int C, int OH, int OW, salun_stream_t stream);
 
+/* ----------------------------------------------------------------- K27 --
+ * Forward-only fp32 convolution for arbitrary map sizes with the epilogue of a folded BatchNorm
+ * (csrc/salun_conv_infer.hip), and the three small kernels the classifier evaluation needs around it.
+ * Replaces, in eval mode,  torchvision.models.resnet34(...)  DDPM/classifier_evaluation.py:135-143  layer by layer:
+ * nn.Conv2d(bias=False) -> nn.BatchNorm2d (running statistics) [-> + identity] [-> ReLU].
+ *   y[n,k,p,q] = act( conv(x, w)[n,k,p,q] * scale[k] + shift[k] + addend[n,k,p,q] )
+ * x [N, C, H, W], w [K, C, R, R] (OIHW, read in place), y and addend [N, K, P, Q], scale and shift [K]; scale, shift and
+ * addend may each be NULL (the term is skipped); relu != 0: act(o) = o < 0 ? 0 : o (a NaN stays a NaN).  `pad` is the
+ * low-side padding; P and Q are the caller's.  The epilogue operations are applied in the order written, each rounded by
+ * itself (no fused multiply-add).  The reduction is an exact-fp32 FMA chain on v_mfma_f32_32x32x2_f32 as in K8.
+ * Domain: R in {1, 3, 7}; stride in {1, 2}; 0 <= pad < R; K a multiple of 32 (<= 65536); 1 <= C <= 65536, a multiple
+ * of 8 unless R == 7; 1 <= H, W, P, Q <= 1024 with the first tap of the last output row / column inside the padded
+ * input ((P - 1) stride - pad < H, likewise Q); N >= 1, N P Q <= 2^40.  N P Q need not fill a tile: the last pixel
+ * tile is masked.  Indexing is 64-bit.
+ * `tile`: SALUN_INFER_TILE_AUTO picks pixels x channels from the problem (the largest of 128x128, 128x64, 64x64 that
+ * still gives every CU a workgroup); the other values force one (tests, tuning).  Every tile gives the same bits.
+ * One launch, no workspace, no atomics: the same inputs give the same bits, and an image's output does not depend on
+ * the rest of the batch.
+ * SALUN_EINVAL (nothing is written): anything outside the domain, a NULL x, w or y, addend == y, x == y, a pointer off
+ * 4-byte alignment.
+ * salun_conv2d_infer_route: the label of the plan the call would run, from the plan function the launch uses; touches
+ * no device.  infer<R,stride>/<pixels>x<channels>/<fast|generic>/B<workgroups>; fast: C % 16 == 0 (tap-outermost
+ * reduction), generic: any C (OIHW-order reduction, zero-padded to a multiple of 16).  SALUN_ENOSPC: buf too short. */
+#define SALUN_INFER_TILE_AUTO 0
+#define SALUN_INFER_TILE_64X64 1
+#define SALUN_INFER_TILE_128X64 2
+#define SALUN_INFER_TILE_128X128 3
+int salun_conv2d_infer(const float *x /*dev*/, const float *w /*dev*/, const float *scale /*dev, K, or NULL*/,
+                       const float *shift /*dev, K, or NULL*/, const float *addend /*dev, N*K*P*Q, or NULL*/,
+                       float *y /*dev, N*K*P*Q*/, int N, int C, int H, int W, int K, int R, int stride, int pad, int P,
+                       int Q, int relu, int tile, salun_stream_t stream);
+int salun_conv2d_infer_route(int N, int C, int H, int W, int K, int R, int stride, int pad, int P, int Q, int tile,
+                             char *buf, size_t buflen);
+
+/* MaxPool2d(kernel_size=3, stride=2, padding=1), forward only (csrc/salun_pool.hip, beside K24).
+ * Replaces  resnet34().maxpool  (DDPM/classifier_evaluation.py:135).
+ * x [NC, H, W] (contiguous), y [NC, (H+1)/2, (W+1)/2], any H, W >= 1.  Padding acts as -inf.  Selection is that of
+ * torch.nn.functional.max_pool2d: scan the window row by row, left to right, from -inf and take a value when it is
+ * greater than the running maximum or is NaN - the first of equal maxima wins, a NaN wins, +0 after -0 does not
+ * replace it.  One launch, one output per thread, 64-bit indexing.
+ * SALUN_EINVAL (nothing is written): NC < 1, H or W < 1 or > 2^20, a NULL pointer, y == x, a pointer off 4-byte
+ * alignment. */
+int salun_maxpool3x3s2_forward(const float *x /*dev*/, float *y /*dev, NC*((H+1)/2)*((W+1)/2)*/, int64_t NC, int H,
+                               int W, salun_stream_t stream);
+
+/* transforms.ToTensor() + transforms.Normalize(mean, std) of uint8 images (csrc/salun_imgnorm.hip).
+ * Replaces  DDPM/classifier_evaluation.py:94-100  (after the Resize, which is K26).
+ * src [B, H, W, C] uint8 (K26's output layout), dst [B, C, H, W] fp32:
+ *   dst[b,c,h,w] = ((float(src[b,h,w,c]) / 255) - mean[c]) / std[c],  every step rounded to fp32 - bit for bit what
+ * torch computes.  salun_u8_norm_table fills the 256 x C table of that expression in HOST memory (table[c * 256 + u];
+ * host arithmetic, no device call); the caller uploads it once and passes the device copy to salun_u8_to_chw_norm.
+ * SALUN_EINVAL (nothing is written): B, H or W < 1, C outside [1, SALUN_U8_NORM_MAX_C], a NULL pointer, table or dst
+ * off 4-byte alignment. */
+#define SALUN_U8_NORM_MAX_C 4
+int salun_u8_norm_table(const float *mean /*host, C*/, const float *std /*host, C*/, int C, float *table /*host, 256*C*/);
+int salun_u8_to_chw_norm(const uint8_t *src /*dev, B*H*W*C*/, const float *table /*dev, 256*C*/,
+                         float *dst /*dev, B*C*H*W*/, int64_t B, int H, int W, int C, salun_stream_t stream);
+
+/* The evaluation head (csrc/salun_cls_head.hip, beside K23): pool -> fc -> softmax as salun_cls_head_forward (same
+ * statements, same rounding points), then the figures of DDPM/classifier_evaluation.py:22-36 for ONE label shared by
+ * the whole batch.  Replaces  model.avgpool / model.fc  and  validate()'s  argmax / softmax / log / sums.
+ * Writes logits [B, K] and p [B, K] and ADDS to caller-owned device meters (each may be NULL; no host synchronisation):
+ *   *entropy_sum (float64) += sum_b -(sum_k p[b,k] * logf(p[b,k]))      *prob_sum (float64) += sum_b p[b, label]
+ *   *hits (int64) += #{b : lowest index of the row's maximum == label}  *count (int64) += B
+ * zero_safe == 0: every entropy term is the reference's fp32 expression p * log(p); a probability that underflowed
+ * to 0 gives 0 * -inf = NaN for the sample and the sum, as the reference does.  zero_safe != 0: such a term is 0.
+ * The per-sample values are folded in float64 in one fixed order by the last workgroup to finish (a ticket in ws, cleared
+ * by a memset ahead of the ONE launch); no floating-point atomics: the same inputs give the same bits.
+ * ws: salun_cls_head_eval_workspace_bytes(B, C, K) bytes (0: outside the limits).
+ * SALUN_EINVAL: the limits of salun_cls_head_forward, label outside [0, K), a NULL x, w, bias, logits, p or ws, a
+ * pointer off its element's alignment.  SALUN_ENOSPC: ws_bytes short of the query. */
+size_t salun_cls_head_eval_workspace_bytes(int64_t B, int C, int K);
+int salun_cls_head_eval(const float *x /*dev, B*C*HW*/, const float *w /*dev, K*C*/, const float *bias /*dev, K*/,
+                        int label, float *logits /*dev, B*K*/, float *p /*dev, B*K*/,
+                        double *entropy_sum /*dev or NULL*/, double *prob_sum /*dev or NULL*/,
+                        int64_t *hits /*dev or NULL*/, int64_t *count /*dev or NULL*/, int64_t B, int C, int HW, int K,
+                        int zero_safe, void *ws /*dev*/, size_t ws_bytes, salun_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -70,6 +70,8 @@ SALUN_SVC_MAX_D = 16
 SALUN_SVC_WIDE_MAX_D = 1024
 SALUN_RESAMPLE_MAX_SIDE = 1024
 SALUN_RESAMPLE_MAX_LDS = 65536
+SALUN_INFER_TILE_AUTO, SALUN_INFER_TILE_64X64, SALUN_INFER_TILE_128X64, SALUN_INFER_TILE_128X128 = 0, 1, 2, 3
+SALUN_U8_NORM_MAX_C = 4
 
 # name -> (restype, argtypes); mirrors include/salun.h one to one
 # (tests/test_cabi.py checks this table against the header and the .so).
@@ -238,6 +240,14 @@ SIGNATURES = {
     "salun_resample_u8_lds_bytes": (c_size_t, [c_int] * 5),
     "salun_resample_u8_table": (c_int, [c_int, c_int, c_void_p, c_size_t, ctypes.POINTER(c_int)]),
     "salun_resample_u8": (c_int, [c_void_p, c_void_p, c_int64] + [c_int] * 5 + [c_void_p]),
+    "salun_conv2d_infer": (c_int, [c_void_p] * 6 + [c_int] * 12 + [c_void_p]),
+    "salun_conv2d_infer_route": (c_int, [c_int] * 11 + [ctypes.c_char_p, c_size_t]),
+    "salun_maxpool3x3s2_forward": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    "salun_u8_norm_table": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    "salun_u8_to_chw_norm": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
+    "salun_cls_head_eval_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "salun_cls_head_eval": (c_int, [c_void_p] * 3 + [c_int] + [c_void_p] * 6 + [c_int64, c_int, c_int, c_int, c_int,
+                                                                                c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

@@ -1,0 +1,84 @@
+"""Inference convolution, pool and image normalisation on K27 and its companions (csrc/salun_conv_infer.hip,
+salun_pool.hip, salun_imgnorm.hip).
+
+Thin callers in the pattern of pool.py: inside the kernels' domain a call is one launch; outside it (a dtype or device
+the kernels do not take, autocast, a filter or stride K27 refuses) the library op runs — LOUDLY: every such call is
+counted in `LIBRARY_INFER_CALLS`, by reason, as `conv.LIBRARY_CONV_CALLS` counts the training convolutions that went
+to the library.  Nothing here records an autograd graph: the kernels are forward only, and a tensor that requires grad
+is one of the reasons a call goes to the library.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+import torch.nn.functional as F
+
+from . import _lib, ops_infer
+
+# calls that went to the library instead of K27 / the pool / the normalise kernel, by reason
+LIBRARY_INFER_CALLS = {"conv_shape": 0, "conv_dtype_or_autocast": 0, "conv_requires_grad": 0, "pool_dtype_or_autocast": 0,
+                       "norm_shape": 0}
+
+
+def library_infer_calls() -> int:
+    return sum(LIBRARY_INFER_CALLS.values())
+
+
+def reset_library_infer_calls() -> None:
+    for k in LIBRARY_INFER_CALLS:
+        LIBRARY_INFER_CALLS[k] = 0
+
+
+def _library_conv(x, w, scale, shift, addend, relu, stride, pad):
+    y = F.conv2d(x, w, None, stride, pad)
+    if scale is not None:
+        y = y * scale.view(1, -1, 1, 1)
+    if shift is not None:
+        y = y + shift.view(1, -1, 1, 1)
+    if addend is not None:
+        y = y + addend
+    return F.relu(y) if relu else y
+
+
+def conv_bn_act(x: torch.Tensor, w: torch.Tensor, scale: Optional[torch.Tensor] = None,
+                shift: Optional[torch.Tensor] = None, addend: Optional[torch.Tensor] = None, relu: bool = False,
+                stride: int = 1, pad: int = 0, out: Optional[torch.Tensor] = None,
+                tile: int = _lib.SALUN_INFER_TILE_AUTO) -> torch.Tensor:
+    """act(conv2d(x, w, stride, pad) * scale[k] + shift[k] + addend), forward only."""
+    ts = [t for t in (x, w, scale, shift, addend) if t is not None]
+    if not all(t.is_cuda and t.dtype == torch.float32 for t in ts) or torch.is_autocast_enabled():
+        LIBRARY_INFER_CALLS["conv_dtype_or_autocast"] += 1
+        return _library_conv(x, w, scale, shift, addend, relu, stride, pad)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in ts):
+        LIBRARY_INFER_CALLS["conv_requires_grad"] += 1
+        return _library_conv(x, w, scale, shift, addend, relu, stride, pad)
+    ok = x.dim() == 4 and w.dim() == 4 and w.shape[2] == w.shape[3] and w.shape[1] == x.shape[1]
+    if ok:
+        N, C, H, W = (int(v) for v in x.shape)
+        K, R = int(w.shape[0]), int(w.shape[2])
+        P, Q = ops_infer.conv_out_size(H, R, stride, pad), ops_infer.conv_out_size(W, R, stride, pad)
+        ok = N >= 1 and P >= 1 and Q >= 1 and ops_infer.conv2d_infer_route(N, C, H, W, K, R, stride, pad, P, Q, tile) is not None
+    if not ok:
+        LIBRARY_INFER_CALLS["conv_shape"] += 1
+        return _library_conv(x, w, scale, shift, addend, relu, stride, pad)
+    return ops_infer.conv2d_infer(x.contiguous(), w.contiguous(), scale, shift,
+                                  None if addend is None else addend.contiguous(), relu, stride, pad, out, tile)
+
+
+def maxpool3x3s2(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """max_pool2d(x, kernel_size=3, stride=2, padding=1) with the library's selection rule."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4) or torch.is_autocast_enabled() or \
+            (torch.is_grad_enabled() and x.requires_grad):
+        LIBRARY_INFER_CALLS["pool_dtype_or_autocast"] += 1
+        return F.max_pool2d(x, 3, 2, 1)
+    return ops_infer.maxpool3x3s2(x.contiguous(), out)
+
+
+def u8_to_chw_norm(src: torch.Tensor, table: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Normalize(ToTensor(src)) of uint8 [B, H, W, C] device images through the [C, 256] table of ops_infer.u8_norm_table."""
+    if not (src.is_cuda and src.dtype == torch.uint8 and src.dim() == 4 and 1 <= src.shape[3] <= _lib.SALUN_U8_NORM_MAX_C):
+        LIBRARY_INFER_CALLS["norm_shape"] += 1
+        idx = src.long().permute(0, 3, 1, 2)
+        return torch.stack([table.to(src.device)[c][idx[:, c]] for c in range(idx.shape[1])], 1)
+    return ops_infer.u8_to_chw_norm(src.contiguous(), table, out)

@@ -242,6 +242,129 @@ __global__ __launch_bounds__(SALUN_BLOCK) void k_cls_head_bwd_w(const float *__r
   }
 }
 
+// ---- the evaluation head: pool -> fc -> softmax of K23's forward (the same statements, the same rounding points), then
+// the three figures DDPM/classifier_evaluation.py reports, for ONE label shared by the whole batch:
+//   ent_b  = -(sum_k p_k * logf(p_k))   per-lane chain over k = tid, tid + 256, ..., tree, fold; zero_safe: a term with
+//            p_k == 0 is 0 instead of 0 * -inf = NaN
+//   prob_b = p[b, label]                hit_b = (lowest index of the row's maximum == label)
+// ent_b and prob_b go to `ws` (floats 4 .. 4 + 2B after the 16-byte ticket); the workgroup with the last ticket folds
+// them in float64 in index order and adds the totals to the caller's meters.
+__global__ __launch_bounds__(SALUN_BLOCK) void k_cls_head_eval(
+    const float *__restrict__ x, const float *__restrict__ w, const float *__restrict__ bias, int label,
+    float *__restrict__ logits, float *__restrict__ p, float *per, double *__restrict__ entropy_sum,
+    double *__restrict__ prob_sum, unsigned long long *__restrict__ hits, long long *__restrict__ count, int64_t B, int C,
+    int HW, int K, int vec, int zero_safe, unsigned int *ticket) {
+  extern __shared__ float4 dyn4[];
+  float *pool_s = reinterpret_cast<float *>(dyn4);
+  float *logit_s = pool_s + ((C + 3) & ~3);
+  float *exp_s = logit_s + ((K + 3) & ~3);
+  __shared__ float red_v[4];
+  __shared__ int red_i[4];
+  __shared__ double red_d[4];
+  __shared__ unsigned int s_last;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float hwf = static_cast<float>(HW);
+  unsigned int my_hits = 0;  // thread 0 only
+
+  for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
+    for (int c = tid; c < C; c += SALUN_BLOCK) {
+      const float *xc = x + (b * C + c) * static_cast<int64_t>(HW);
+      float acc = 0.0f;
+      if (vec) {
+        const float4 *x4 = reinterpret_cast<const float4 *>(xc);
+        for (int j = 0; j < (HW >> 2); ++j) {
+          const float4 v = x4[j];
+          acc = acc + ((v.x + v.y) + (v.z + v.w));
+        }
+      } else {
+        for (int j = 0; j < HW; ++j) acc = acc + xc[j];
+      }
+      pool_s[c] = acc / hwf;
+    }
+    __syncthreads();
+    for (int k = wave; k < K; k += 4) {
+      const float *wk = w + static_cast<int64_t>(k) * C;
+      float acc = 0.0f;
+      for (int c = lane; c < C; c += 64) acc = fmaf(pool_s[c], wk[c], acc);
+      acc = wave_sum_f32(acc);
+      if (lane == 0) {
+        const float l = acc + bias[k];
+        logit_s[k] = l;
+        logits[b * K + k] = l;
+      }
+    }
+    __syncthreads();
+    float mv = -INFINITY;
+    int mi = 0x7FFFFFFF;
+    for (int k = tid; k < K; k += SALUN_BLOCK) {
+      const float v = logit_s[k];
+      if (v > mv || mi == 0x7FFFFFFF) { mv = v; mi = k; }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const float ov = __shfl_down(mv, off, 64);
+      const int oi = __shfl_down(mi, off, 64);
+      if (oi != 0x7FFFFFFF && (mi == 0x7FFFFFFF || ov > mv || (ov == mv && oi < mi))) { mv = ov; mi = oi; }
+    }
+    if (lane == 0) { red_v[wave] = mv; red_i[wave] = mi; }
+    __syncthreads();
+    mv = red_v[0];
+    mi = red_i[0];
+#pragma unroll
+    for (int q = 1; q < 4; ++q) {
+      const float ov = red_v[q];
+      const int oi = red_i[q];
+      if (oi != 0x7FFFFFFF && (mi == 0x7FFFFFFF || ov > mv || (ov == mv && oi < mi))) { mv = ov; mi = oi; }
+    }
+    __syncthreads();
+    float part = 0.0f;
+    for (int k = tid; k < K; k += SALUN_BLOCK) {
+      const float e = expf(logit_s[k] - mv);
+      exp_s[k] = e;
+      part = part + e;
+    }
+    const float S = block_sum_f32(part, red_v);
+    float epart = 0.0f;
+    for (int k = tid; k < K; k += SALUN_BLOCK) {
+      const float pk = exp_s[k] / S;
+      p[b * K + k] = pk;
+      const float term = (zero_safe && pk == 0.0f) ? 0.0f : pk * logf(pk);
+      epart = epart + term;
+    }
+    const float esum = block_sum_f32(epart, red_v);
+    if (tid == 0) {
+      per[b] = -esum;
+      per[B + b] = exp_s[label] / S;
+      if (mi == label) ++my_hits;
+    }
+    __syncthreads();
+  }
+
+  if (tid == 0) {
+    if (hits && my_hits) atomicAdd(hits, static_cast<unsigned long long>(my_hits));
+    __threadfence();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    s_last = (atomicAdd(ticket, 1u) == gridDim.x - 1) ? 1u : 0u;
+  }
+  __syncthreads();
+  if (!s_last) return;
+  __threadfence();
+  double e_acc = 0.0, p_acc = 0.0;
+  for (int64_t b = tid; b < B; b += SALUN_BLOCK) {
+    const int eb = __hip_atomic_load(reinterpret_cast<int *>(per) + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int pb = __hip_atomic_load(reinterpret_cast<int *>(per) + B + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    e_acc += static_cast<double>(__int_as_float(eb));
+    p_acc += static_cast<double>(__int_as_float(pb));
+  }
+  const double e_tot = salun_block_sum(e_acc, red_d);
+  const double p_tot = salun_block_sum(p_acc, red_d);
+  if (tid == 0) {
+    if (entropy_sum) *entropy_sum += e_tot;
+    if (prob_sum) *prob_sum += p_tot;
+    if (count) *count += static_cast<long long>(B);
+  }
+}
+
 bool shape_ok(int64_t B, int C, int HW, int K) {
   return B >= 1 && B <= (int64_t(1) << 31) - 1 && C >= 1 && C <= MAX_C && HW >= 1 && HW <= (1 << 20) && K >= 1 &&
          K <= MAX_K;
@@ -305,5 +428,33 @@ SALUN_EXPORT int salun_cls_head_backward(const float *p, const float *pooled, co
                        accumulate_w ? 1 : 0, accumulate_b ? 1 : 0, B, C, K, ctiles);
     SALUN_LAUNCH_CHECK();
   }
+  return SALUN_OK;
+}
+
+SALUN_EXPORT size_t salun_cls_head_eval_workspace_bytes(int64_t B, int C, int K) {
+  if (B < 1 || B > (int64_t(1) << 31) - 1 || C < 1 || C > MAX_C || K < 1 || K > MAX_K) return 0;
+  return 16 + 2 * sizeof(float) * static_cast<size_t>(B);  // the ticket, then ent[B] and prob[B]
+}
+
+SALUN_EXPORT int salun_cls_head_eval(const float *x, const float *w, const float *bias, int label, float *logits, float *p,
+                                     double *entropy_sum, double *prob_sum, int64_t *hits, int64_t *count, int64_t B,
+                                     int C, int HW, int K, int zero_safe, void *ws, size_t ws_bytes,
+                                     salun_stream_t stream) {
+  if (!shape_ok(B, C, HW, K) || label < 0 || label >= K) return SALUN_EINVAL;
+  if (!x || !w || !bias || !logits || !p || !ws) return SALUN_EINVAL;
+  if (!salun_aligned4(x) || !salun_aligned4(w) || !salun_aligned4(bias) || !salun_aligned4(logits) || !salun_aligned4(p) ||
+      !aligned8(entropy_sum) || !aligned8(prob_sum) || !aligned8(hits) || !aligned8(count) || !salun_aligned4(ws))
+    return SALUN_EINVAL;
+  if (ws_bytes < salun_cls_head_eval_workspace_bytes(B, C, K)) return SALUN_ENOSPC;
+  hipStream_t st = salun_hip_stream(stream);
+  unsigned int *ticket = static_cast<unsigned int *>(ws);
+  if (hipMemsetAsync(ticket, 0, sizeof(unsigned int), st) != hipSuccess) return SALUN_EIO;
+  const int vec = salun_aligned16(x) && (HW % 4 == 0);
+  const size_t lds = sizeof(float) * static_cast<size_t>(((C + 3) & ~3) + 2 * ((K + 3) & ~3));
+  hipLaunchKernelGGL(k_cls_head_eval, dim3(salun_grid_for(B, 1)), dim3(SALUN_BLOCK), lds, st, x, w, bias, label, logits, p,
+                     reinterpret_cast<float *>(ticket + 4), entropy_sum, prob_sum,
+                     reinterpret_cast<unsigned long long *>(hits), reinterpret_cast<long long *>(count), B, C, HW, K, vec,
+                     zero_safe ? 1 : 0, ticket);
+  SALUN_LAUNCH_CHECK();
   return SALUN_OK;
 }

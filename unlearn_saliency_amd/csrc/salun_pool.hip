@@ -123,7 +123,49 @@ bool shape_ok(int64_t NC, int H, int W) {
   return NC <= (int64_t(1) << 62) / (static_cast<int64_t>(H) * W);
 }
 
+// ---- MaxPool2d(kernel 3, stride 2, padding 1), forward only: the pool behind the stem of an ImageNet-style ResNet.
+// One output per thread, grid-stride.  The window is scanned row by row, left to right, from (-inf); positions in the
+// padding are skipped (padding acts as -inf); a value is taken when it is greater than the running maximum or is NaN:
+// F.max_pool2d's rule (first of equal maxima, NaN wins, +0 after -0 does not replace it).
+__global__ __launch_bounds__(SALUN_BLOCK) void k_maxpool3x3s2_fwd(const float *__restrict__ x, float *__restrict__ y,
+                                                                  int64_t outs, int H, int W, int OH, int OW) {
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * SALUN_BLOCK;
+  const int64_t plane_out = static_cast<int64_t>(OH) * OW;
+  for (int64_t o = static_cast<int64_t>(blockIdx.x) * SALUN_BLOCK + threadIdx.x; o < outs; o += stride) {
+    const int64_t nc = o / plane_out;
+    const int rem = static_cast<int>(o - nc * plane_out);
+    const int oh = rem / OW, ow = rem - oh * OW;
+    const float *xp = x + nc * (static_cast<int64_t>(H) * W);
+    float m = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      const int ih = 2 * oh - 1 + r;
+      if (ih < 0 || ih >= H) continue;
+#pragma unroll
+      for (int s = 0; s < 3; ++s) {
+        const int iw = 2 * ow - 1 + s;
+        if (iw < 0 || iw >= W) continue;
+        const float v = xp[static_cast<int64_t>(ih) * W + iw];
+        if (v > m || v != v) m = v;
+      }
+    }
+    y[o] = m;
+  }
+}
+
 }  // namespace
+
+SALUN_EXPORT int salun_maxpool3x3s2_forward(const float *x, float *y, int64_t NC, int H, int W, salun_stream_t stream) {
+  if (NC < 1 || H < 1 || W < 1 || H > (1 << 20) || W > (1 << 20)) return SALUN_EINVAL;
+  if (NC > (int64_t(1) << 62) / (static_cast<int64_t>(H) * W)) return SALUN_EINVAL;
+  if (!x || !y || x == y || !salun_aligned4(x) || !salun_aligned4(y)) return SALUN_EINVAL;
+  const int OH = (H + 1) / 2, OW = (W + 1) / 2;
+  const int64_t outs = NC * OH * OW;
+  hipLaunchKernelGGL(k_maxpool3x3s2_fwd, dim3(salun_grid_for(outs, SALUN_BLOCK)), dim3(SALUN_BLOCK), 0,
+                     salun_hip_stream(stream), x, y, outs, H, W, OH, OW);
+  SALUN_LAUNCH_CHECK();
+  return SALUN_OK;
+}
 
 SALUN_EXPORT int salun_maxpool2x2_forward(const float *x, float *y, uint8_t *idx, int64_t NC, int H, int W,
                                           salun_stream_t stream) {

@@ -1,0 +1,132 @@
+"""Tensor-level wrappers of K27 and the kernels around it (csrc/salun_conv_infer.hip, salun_pool.hip,
+salun_imgnorm.hip, salun_cls_head.hip; include/salun.h): the forward-only convolution with a folded-BatchNorm epilogue,
+the 3 x 3 / stride-2 max-pool, uint8 HWC -> normalised fp32 CHW, and the evaluation head.
+
+Same conventions as ops.py: device tensors only, raw pointers and the current stream handed to libsalun.so, a failing
+call raises `SalunError`.  Every function takes an optional `out` so that a caller with its own activation buffers
+(DDPM/models/resnet34.InferencePlan) allocates nothing per call.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import c_int64, c_size_t, c_void_p, check
+from .ops import _dev, _stream, workspace
+
+
+def conv_out_size(size: int, R: int, stride: int, pad: int) -> int:
+    return (size + 2 * pad - R) // stride + 1
+
+
+def conv2d_infer_route(N, C, H, W, K, R, stride, pad, P, Q, tile: int = _lib.SALUN_INFER_TILE_AUTO) -> Optional[str]:
+    """The label of the plan a call would run, or None where K27 refuses the shape.  Host arithmetic only."""
+    buf = ctypes.create_string_buffer(96)
+    rc = _lib.lib().salun_conv2d_infer_route(N, C, H, W, K, R, stride, pad, P, Q, tile, buf, 96)
+    if rc == _lib.SALUN_EINVAL:
+        return None
+    check(rc, "salun_conv2d_infer_route")
+    return buf.value.decode()
+
+
+def conv2d_infer(x: torch.Tensor, w: torch.Tensor, scale: Optional[torch.Tensor] = None,
+                 shift: Optional[torch.Tensor] = None, addend: Optional[torch.Tensor] = None, relu: bool = False,
+                 stride: int = 1, pad: int = 0, out: Optional[torch.Tensor] = None,
+                 tile: int = _lib.SALUN_INFER_TILE_AUTO) -> torch.Tensor:
+    """act(conv(x, w) * scale[k] + shift[k] + addend): x [N, C, H, W], w [K, C, R, R] -> [N, K, P, Q].  One launch."""
+    N, C, H, W = (int(v) for v in x.shape)
+    K, Cw, R, S = (int(v) for v in w.shape)
+    if Cw != C or R != S:
+        raise ValueError(f"conv2d_infer: weight {tuple(w.shape)} does not fit x {tuple(x.shape)}")
+    P, Q = conv_out_size(H, R, stride, pad), conv_out_size(W, R, stride, pad)
+    if out is None:
+        out = torch.empty((N, K, P, Q), dtype=torch.float32, device=x.device)
+    elif out.numel() != N * K * P * Q:
+        raise ValueError("conv2d_infer: out has the wrong size")
+    if addend is not None and addend.numel() != out.numel():
+        raise ValueError("conv2d_infer: addend has the wrong size")
+    check(_lib.lib().salun_conv2d_infer(_dev(x, torch.float32, "x"), _dev(w, torch.float32, "w"),
+                                        _dev(scale, torch.float32, "scale", True),
+                                        _dev(shift, torch.float32, "shift", True),
+                                        _dev(addend, torch.float32, "addend", True), _dev(out, torch.float32, "out"),
+                                        N, C, H, W, K, R, stride, pad, P, Q, int(bool(relu)), tile, _stream()),
+          "salun_conv2d_infer")
+    return out.view(N, K, P, Q)
+
+
+def maxpool3x3s2(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """F.max_pool2d(x, 3, 2, 1) of x [N, C, H, W] -> [N, C, (H+1)/2, (W+1)/2]."""
+    N, C, H, W = (int(v) for v in x.shape)
+    OH, OW = (H + 1) // 2, (W + 1) // 2
+    if out is None:
+        out = torch.empty((N, C, OH, OW), dtype=torch.float32, device=x.device)
+    elif out.numel() != N * C * OH * OW:
+        raise ValueError("maxpool3x3s2: out has the wrong size")
+    check(_lib.lib().salun_maxpool3x3s2_forward(_dev(x, torch.float32, "x"), _dev(out, torch.float32, "out"),
+                                                c_int64(N * C), H, W, _stream()), "salun_maxpool3x3s2_forward")
+    return out.view(N, C, OH, OW)
+
+
+def u8_norm_table(mean, std) -> torch.Tensor:
+    """The 256 x C table of ((u / 255) - mean[c]) / std[c] in fp32 steps, as a HOST tensor [C, 256]."""
+    m, s = np.asarray(mean, np.float32), np.asarray(std, np.float32)
+    if m.ndim != 1 or m.shape != s.shape:
+        raise ValueError("u8_norm_table: mean and std are two vectors of one length")
+    table = np.empty((m.size, 256), np.float32)
+    check(_lib.lib().salun_u8_norm_table(c_void_p(m.ctypes.data), c_void_p(s.ctypes.data), int(m.size),
+                                         c_void_p(table.ctypes.data)), "salun_u8_norm_table")
+    return torch.from_numpy(table)
+
+
+def u8_to_chw_norm(src: torch.Tensor, table: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """src uint8 [B, H, W, C], table fp32 [C, 256] on the device -> fp32 [B, C, H, W] = Normalize(ToTensor(src))."""
+    B, H, W, C = (int(v) for v in src.shape)
+    if tuple(table.shape) != (C, 256):
+        raise ValueError(f"u8_to_chw_norm: table {tuple(table.shape)} must be ({C}, 256)")
+    if out is None:
+        out = torch.empty((B, C, H, W), dtype=torch.float32, device=src.device)
+    elif out.numel() != B * C * H * W:
+        raise ValueError("u8_to_chw_norm: out has the wrong size")
+    check(_lib.lib().salun_u8_to_chw_norm(_dev(src, torch.uint8, "src"), _dev(table, torch.float32, "table"),
+                                          _dev(out, torch.float32, "out"), c_int64(B), H, W, C, _stream()),
+          "salun_u8_to_chw_norm")
+    return out.view(B, C, H, W)
+
+
+class EvalMeters:
+    """The device-side running sums of the evaluation head: no host synchronisation until `read()`."""
+
+    def __init__(self, device):
+        self.f = torch.zeros(2, dtype=torch.float64, device=device)   # entropy_sum, prob_sum
+        self.i = torch.zeros(2, dtype=torch.int64, device=device)     # hits, count
+
+    def read(self) -> dict:
+        f, i = self.f.cpu(), self.i.cpu()
+        return {"entropy_sum": float(f[0]), "prob_sum": float(f[1]), "hits": int(i[0]), "count": int(i[1])}
+
+
+def cls_head_eval(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, label: int, meters: Optional[EvalMeters],
+                  zero_safe: bool = False):
+    """pool -> fc -> softmax of x [B, C, H, W]; adds the batch's entropy, p[:, label], hits and count to `meters`.
+    -> (logits [B, K], p [B, K])."""
+    B, C = int(x.shape[0]), int(x.shape[1])
+    HW = int(x.numel() // (B * C))
+    K = int(weight.shape[0])
+    L = _lib.lib()
+    logits = torch.empty((B, K), dtype=torch.float32, device=x.device)
+    p = torch.empty((B, K), dtype=torch.float32, device=x.device)
+    nbytes = L.salun_cls_head_eval_workspace_bytes(c_int64(B), C, K)
+    ws = workspace(nbytes, x.device, "cls_eval")
+    f = c_void_p(meters.f.data_ptr()) if meters is not None else c_void_p(None)
+    f1 = c_void_p(meters.f.data_ptr() + 8) if meters is not None else c_void_p(None)
+    i0 = c_void_p(meters.i.data_ptr()) if meters is not None else c_void_p(None)
+    i1 = c_void_p(meters.i.data_ptr() + 8) if meters is not None else c_void_p(None)
+    check(L.salun_cls_head_eval(_dev(x, torch.float32, "x"), _dev(weight, torch.float32, "weight"),
+                                _dev(bias, torch.float32, "bias"), int(label), c_void_p(logits.data_ptr()),
+                                c_void_p(p.data_ptr()), f, f1, i0, i1, c_int64(B), C, HW, K, int(bool(zero_safe)),
+                                c_void_p(ws.data_ptr()), c_size_t(ws.numel()), _stream()), "salun_cls_head_eval")
+    return logits, p

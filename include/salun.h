@@ -1129,6 +1129,51 @@ int salun_cls_head_eval(const float *x /*dev, B*C*HW*/, const float *w /*dev, K*
                         int64_t *hits /*dev or NULL*/, int64_t *count /*dev or NULL*/, int64_t B, int C, int HW, int K,
                         int zero_safe, void *ws /*dev*/, size_t ws_bytes, salun_stream_t stream);
 
+/* ----------------------------------------------------------------- K28 --
+ * GroupNorm (+ SiLU) forward for groups too large for one workgroup (csrc/salun_gn_split.hip).
+ * Replaces  Normalize(in_channels) = torch.nn.GroupNorm(32, C, eps=1e-6, affine=True)  followed by  nonlinearity(x) =
+ * x * sigmoid(x)  in ldm/modules/diffusionmodules/model.py:33-39 (ResnetBlock, AttnBlock, Encoder.norm_out), at the
+ * map sizes of the first-stage encoder, where salun_gn_forward refuses (H W not a power of two, cpg HW > 262144).
+ *   y = [silu](gamma[c] * (x - mean[n,g]) * rstd[n,g] + beta[c]),  x and y [N, C, HW], statistics over the cpg * HW
+ * contiguous values of an (image, group), biased variance.  The arithmetic is salun_gn_forward's, statement for
+ * statement: lanes add float4 trees in fp32 and fold into doubles every SALUN_GN_SPLIT_FLUSH float4s; block sums, the
+ * fold of the slabs, mean and variance are in double; a = rstd * gamma[c], b = beta[c] - mean * a, o = x * a + b, each
+ * rounded by itself; SiLU is o * (1 / (1 + expf(-o))).
+ * A group is cut into S = ceil(cpg HW / 4 / slab) slabs of `slab` float4s (the last may be shorter; a boundary may fall
+ * inside a channel or between channels).  Two launches over a grid of N G S, no atomics: the first writes one (sum, sum
+ * of squares) pair of doubles per slab to ws, the second folds a group's S pairs in index order in every workgroup of
+ * the group, writes save_mean / save_rstd [N * G] from slab 0 and applies over its slab.
+ * slab_vec4 == 0: slab = 2048 float4s (8 per lane).  S depends on cpg HW and slab_vec4 only - not on N, not on the
+ * device - so the same inputs give the same bits and an image's output does not depend on the rest of the batch.
+ * Any other slab_vec4 > 0 forces the slab length (tests, tuning).
+ * Domain: N, G >= 1, C % G == 0, HW >= 4 and a multiple of 4, cpg HW < 2^31, N G S < 2^31; x and y 16-byte aligned;
+ * y == x is allowed (an element is read before it is written, the statistics are complete by then).
+ * SALUN_EINVAL (nothing is written): anything outside the domain, slab_vec4 < 0, a NULL pointer, ws off 8-byte
+ * alignment or ws_bytes short of salun_gn_split_workspace_bytes (0 outside the domain).
+ * salun_gn_split_slabs: S (0 outside the domain); touches no device. */
+#define SALUN_GN_SPLIT_FLUSH 16
+size_t salun_gn_split_workspace_bytes(int N, int C, int64_t HW, int G, int slab_vec4);
+int salun_gn_split_slabs(int C, int64_t HW, int G, int slab_vec4);
+int salun_gn_split_forward(const float *x /*dev*/, float *y /*dev*/, const float *gamma /*dev, C*/,
+                           const float *beta /*dev, C*/, float *save_mean /*dev, N*G*/, float *save_rstd /*dev, N*G*/,
+                           int N, int C, int64_t HW, int G, double eps, int silu, int slab_vec4, void *ws /*dev*/,
+                           size_t ws_bytes, salun_stream_t stream);
+
+/* The posterior of the first stage (csrc/salun_vae.hip).  Replaces  DiagonalGaussianDistribution.sample() / .mode()
+ * (ldm/modules/distributions/distributions.py:24-45) and the  scale_factor *  of get_first_stage_encoding
+ * (ldm/models/diffusion/ddpm.py:535-543).
+ * moments [B, Cm, hw] with Cm >= 2 zc: channels [0, zc) are the mean, [zc, 2 zc) the log-variance, further channels are
+ * ignored (the output of a convolution whose K was zero-padded is read in place).  z [B, zc, hw]:
+ *   z = scale * (mean + expf(0.5 * clamp(logvar, -30, 20)) * e),   deterministic != 0: z = scale * mean,
+ * every operation rounded by itself, scale rounded to fp32 first.  e is the value salun_sampler_noise(seed, image_ids,
+ * step = draw, chw = zc * hw) writes at the element's index c * hw + p: an image's latent does not depend on where it
+ * sits in a batch, and another `draw` gives an independent one.
+ * SALUN_EINVAL (nothing is written): zc, hw or B < 1, Cm < 2 zc, draw < 0, B Cm hw > 2^40, a NULL moments or z, NULL
+ * image_ids unless deterministic, moments == z, a pointer off 4-byte alignment. */
+int salun_vae_posterior_sample(const float *moments /*dev, B*Cm*hw*/, int Cm, int zc, int64_t hw, int64_t B,
+                               const int64_t *image_ids /*dev, B*/, uint64_t seed, int64_t draw, double scale,
+                               int deterministic, float *z /*dev, B*zc*hw*/, salun_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

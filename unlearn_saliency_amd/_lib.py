@@ -72,6 +72,7 @@ SALUN_RESAMPLE_MAX_SIDE = 1024
 SALUN_RESAMPLE_MAX_LDS = 65536
 SALUN_INFER_TILE_AUTO, SALUN_INFER_TILE_64X64, SALUN_INFER_TILE_128X64, SALUN_INFER_TILE_128X128 = 0, 1, 2, 3
 SALUN_U8_NORM_MAX_C = 4
+SALUN_GN_SPLIT_FLUSH = 16
 
 # name -> (restype, argtypes); mirrors include/salun.h one to one
 # (tests/test_cabi.py checks this table against the header and the .so).
@@ -248,6 +249,12 @@ SIGNATURES = {
     "salun_cls_head_eval_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "salun_cls_head_eval": (c_int, [c_void_p] * 3 + [c_int] + [c_void_p] * 6 + [c_int64, c_int, c_int, c_int, c_int,
                                                                                 c_void_p, c_size_t, c_void_p]),
+    "salun_gn_split_workspace_bytes": (c_size_t, [c_int, c_int, c_int64, c_int, c_int]),
+    "salun_gn_split_slabs": (c_int, [c_int, c_int64, c_int, c_int]),
+    "salun_gn_split_forward": (c_int, [c_void_p] * 6 + [c_int, c_int, c_int64, c_int, c_double, c_int, c_int, c_void_p,
+                                                         c_size_t, c_void_p]),
+    "salun_vae_posterior_sample": (c_int, [c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_uint64, c_int64,
+                                           c_double, c_int, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -30,8 +30,14 @@ def reset_library_infer_calls() -> None:
         LIBRARY_INFER_CALLS[k] = 0
 
 
-def _library_conv(x, w, scale, shift, addend, relu, stride, pad):
+def _library_conv(x, w, scale, shift, addend, relu, stride, pad, out_size=None):
+    if out_size is not None:       # low-side padding `pad`, zeros on the high side up to the last tap of the asked size
+        R = int(w.shape[2])
+        hi = [max((n - 1) * stride + R - pad - int(s), 0) for n, s in zip(out_size, x.shape[2:])]
+        x, pad = F.pad(x, (pad, hi[1], pad, hi[0])), 0
     y = F.conv2d(x, w, None, stride, pad)
+    if out_size is not None:
+        y = y[:, :, :out_size[0], :out_size[1]]
     if scale is not None:
         y = y * scale.view(1, -1, 1, 1)
     if shift is not None:
@@ -44,26 +50,28 @@ def _library_conv(x, w, scale, shift, addend, relu, stride, pad):
 def conv_bn_act(x: torch.Tensor, w: torch.Tensor, scale: Optional[torch.Tensor] = None,
                 shift: Optional[torch.Tensor] = None, addend: Optional[torch.Tensor] = None, relu: bool = False,
                 stride: int = 1, pad: int = 0, out: Optional[torch.Tensor] = None,
-                tile: int = _lib.SALUN_INFER_TILE_AUTO) -> torch.Tensor:
-    """act(conv2d(x, w, stride, pad) * scale[k] + shift[k] + addend), forward only."""
+                tile: int = _lib.SALUN_INFER_TILE_AUTO, out_size: Optional[tuple] = None) -> torch.Tensor:
+    """act(conv2d(x, w, stride, pad) * scale[k] + shift[k] + addend), forward only.  `out_size` = (P, Q): see
+    ops_infer.conv2d_infer."""
     ts = [t for t in (x, w, scale, shift, addend) if t is not None]
     if not all(t.is_cuda and t.dtype == torch.float32 for t in ts) or torch.is_autocast_enabled():
         LIBRARY_INFER_CALLS["conv_dtype_or_autocast"] += 1
-        return _library_conv(x, w, scale, shift, addend, relu, stride, pad)
+        return _library_conv(x, w, scale, shift, addend, relu, stride, pad, out_size)
     if torch.is_grad_enabled() and any(t.requires_grad for t in ts):
         LIBRARY_INFER_CALLS["conv_requires_grad"] += 1
-        return _library_conv(x, w, scale, shift, addend, relu, stride, pad)
+        return _library_conv(x, w, scale, shift, addend, relu, stride, pad, out_size)
     ok = x.dim() == 4 and w.dim() == 4 and w.shape[2] == w.shape[3] and w.shape[1] == x.shape[1]
     if ok:
         N, C, H, W = (int(v) for v in x.shape)
         K, R = int(w.shape[0]), int(w.shape[2])
-        P, Q = ops_infer.conv_out_size(H, R, stride, pad), ops_infer.conv_out_size(W, R, stride, pad)
+        P, Q = out_size if out_size is not None else \
+            (ops_infer.conv_out_size(H, R, stride, pad), ops_infer.conv_out_size(W, R, stride, pad))
         ok = N >= 1 and P >= 1 and Q >= 1 and ops_infer.conv2d_infer_route(N, C, H, W, K, R, stride, pad, P, Q, tile) is not None
     if not ok:
         LIBRARY_INFER_CALLS["conv_shape"] += 1
-        return _library_conv(x, w, scale, shift, addend, relu, stride, pad)
+        return _library_conv(x, w, scale, shift, addend, relu, stride, pad, out_size)
     return ops_infer.conv2d_infer(x.contiguous(), w.contiguous(), scale, shift,
-                                  None if addend is None else addend.contiguous(), relu, stride, pad, out, tile)
+                                  None if addend is None else addend.contiguous(), relu, stride, pad, out, tile, out_size)
 
 
 def maxpool3x3s2(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:

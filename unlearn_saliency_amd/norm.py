@@ -150,6 +150,38 @@ def fused_gn_act(x: torch.Tensor, gn: nn.GroupNorm, silu: bool = True) -> torch.
 
 _GN_TYPES = {nn.GroupNorm}
 
+# calls of gn_split_act that went to the library instead of K28, by reason
+LIBRARY_GN_SPLIT_CALLS = {"dtype_or_autocast": 0, "requires_grad": 0, "shape": 0}
+
+
+def reset_library_gn_split_calls() -> None:
+    for k in LIBRARY_GN_SPLIT_CALLS:
+        LIBRARY_GN_SPLIT_CALLS[k] = 0
+
+
+def gn_split_act(x: torch.Tensor, gn: nn.GroupNorm, silu: bool = True, out: torch.Tensor = None,
+                 slab_vec4: int = 0) -> torch.Tensor:
+    """`[x * sigmoid(x)](gn(x))`, forward only, on K28 (csrc/salun_gn_split.hip): two launches over (image, group,
+    slab) for maps of any multiple-of-4 size, however large the group.  In the pattern of conv_infer.py: outside the
+    kernel's domain (a dtype or device it does not take, autocast, a tensor that requires grad under grad mode, a map
+    size that is no multiple of 4) the library ops run and the call is counted in `LIBRARY_GN_SPLIT_CALLS`."""
+    from . import ops_infer
+    ts = (x, gn.weight, gn.bias)
+    reason = None
+    if not gn.affine or not all(t.is_cuda and t.dtype == torch.float32 for t in ts) or torch.is_autocast_enabled():
+        reason = "dtype_or_autocast"
+    elif torch.is_grad_enabled() and any(t.requires_grad for t in ts):
+        reason = "requires_grad"
+    elif x.dim() != 4 or x.shape[0] < 1 or ops_infer.gn_split_slabs(int(x.shape[1]), int(x.shape[2] * x.shape[3]),
+                                                                    gn.num_groups, slab_vec4) == 0 or \
+            (x.is_contiguous() and not _on_grid(x)):
+        reason = "shape"
+    if reason is not None:
+        LIBRARY_GN_SPLIT_CALLS[reason] += 1
+        y = gn(x)
+        return y * torch.sigmoid(y) if silu else y
+    return ops_infer.gn_split_forward(x.contiguous(), gn.weight.detach(), gn.bias.detach(), gn.num_groups, gn.eps, silu, out, slab_vec4)
+
 
 def use_fused_bn(model: nn.Module, blocks: bool = True) -> int:
     """Switch this package's CIFAR ResNet (stem + BasicBlocks) or VGG to the fused BN path; with `blocks` each BasicBlock

@@ -36,13 +36,15 @@ def conv2d_infer_route(N, C, H, W, K, R, stride, pad, P, Q, tile: int = _lib.SAL
 def conv2d_infer(x: torch.Tensor, w: torch.Tensor, scale: Optional[torch.Tensor] = None,
                  shift: Optional[torch.Tensor] = None, addend: Optional[torch.Tensor] = None, relu: bool = False,
                  stride: int = 1, pad: int = 0, out: Optional[torch.Tensor] = None,
-                 tile: int = _lib.SALUN_INFER_TILE_AUTO) -> torch.Tensor:
-    """act(conv(x, w) * scale[k] + shift[k] + addend): x [N, C, H, W], w [K, C, R, R] -> [N, K, P, Q].  One launch."""
+                 tile: int = _lib.SALUN_INFER_TILE_AUTO, out_size: Optional[tuple] = None) -> torch.Tensor:
+    """act(conv(x, w) * scale[k] + shift[k] + addend): x [N, C, H, W], w [K, C, R, R] -> [N, K, P, Q].  One launch.
+    `pad` is the low-side padding; `out_size` = (P, Q) asks for more rows / columns than the symmetric formula gives:
+    taps past the high edge read zero (F.pad(x, (0, 1, 0, 1)) + a stride-2 convolution is pad = 0 with P = H / 2)."""
     N, C, H, W = (int(v) for v in x.shape)
     K, Cw, R, S = (int(v) for v in w.shape)
     if Cw != C or R != S:
         raise ValueError(f"conv2d_infer: weight {tuple(w.shape)} does not fit x {tuple(x.shape)}")
-    P, Q = conv_out_size(H, R, stride, pad), conv_out_size(W, R, stride, pad)
+    P, Q = out_size if out_size is not None else (conv_out_size(H, R, stride, pad), conv_out_size(W, R, stride, pad))
     if out is None:
         out = torch.empty((N, K, P, Q), dtype=torch.float32, device=x.device)
     elif out.numel() != N * K * P * Q:
@@ -95,6 +97,52 @@ def u8_to_chw_norm(src: torch.Tensor, table: torch.Tensor, out: Optional[torch.T
                                           _dev(out, torch.float32, "out"), c_int64(B), H, W, C, _stream()),
           "salun_u8_to_chw_norm")
     return out.view(B, C, H, W)
+
+
+def gn_split_slabs(C: int, HW: int, G: int, slab_vec4: int = 0) -> int:
+    """Slabs per group of K28 for the shape (0 where it refuses it).  Host arithmetic only."""
+    return int(_lib.lib().salun_gn_split_slabs(C, c_int64(HW), G, slab_vec4))
+
+
+def gn_split_forward(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups: int, eps: float, silu: bool,
+                     out: Optional[torch.Tensor] = None, slab_vec4: int = 0, want_stats: bool = False):
+    """K28: [silu](group_norm(x)) of x [N, C, H, W] in two launches; `out` may be `x`.  -> y, or (y, mean, rstd)."""
+    N, C = int(x.shape[0]), int(x.shape[1])
+    HW = int(x.numel() // (N * C))
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape:
+        raise ValueError("gn_split_forward: out has the wrong shape")
+    L = _lib.lib()
+    nbytes = int(L.salun_gn_split_workspace_bytes(N, C, c_int64(HW), int(groups), slab_vec4))
+    ws = workspace(nbytes, x.device)
+    stats = torch.empty(2 * N * int(groups), dtype=torch.float32, device=x.device)
+    mean, rstd = stats[:N * int(groups)], stats[N * int(groups):]
+    check(L.salun_gn_split_forward(_dev(x, torch.float32, "x"), _dev(out, torch.float32, "out"),
+                                   _dev(gamma, torch.float32, "weight"), _dev(beta, torch.float32, "bias"),
+                                   c_void_p(mean.data_ptr()), c_void_p(rstd.data_ptr()), N, C, c_int64(HW), int(groups),
+                                   ctypes.c_double(eps), int(bool(silu)), slab_vec4, c_void_p(ws.data_ptr()),
+                                   c_size_t(nbytes), _stream()), "salun_gn_split_forward")
+    return (out, mean, rstd) if want_stats else out
+
+
+def vae_posterior_sample(moments: torch.Tensor, zc: int, image_ids: Optional[torch.Tensor], seed: int, draw: int,
+                         scale: float, deterministic: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """moments [B, Cm, h, w] (Cm >= 2 zc; further channels ignored) -> z [B, zc, h, w] =
+    scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * e), e = ops_sampler.sampler_noise(image_ids, (zc, h, w), seed,
+    step=draw); with `deterministic` scale * mean."""
+    B, Cm, h, w = (int(v) for v in moments.shape)
+    if out is None:
+        out = torch.empty((B, zc, h, w), dtype=torch.float32, device=moments.device)
+    elif out.numel() != B * zc * h * w:
+        raise ValueError("vae_posterior_sample: out has the wrong size")
+    check(_lib.lib().salun_vae_posterior_sample(_dev(moments, torch.float32, "moments"), Cm, int(zc), c_int64(h * w),
+                                                c_int64(B), _dev(image_ids, torch.int64, "image_ids", bool(deterministic)),
+                                                ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), c_int64(int(draw)),
+                                                ctypes.c_double(scale), int(bool(deterministic)),
+                                                _dev(out, torch.float32, "out"), _stream()),
+          "salun_vae_posterior_sample")
+    return out.view(B, zc, h, w)
 
 
 class EvalMeters:

@@ -17,33 +17,10 @@
 // dS^T = P^T*(dP^T - D_q)*scale, dQ^T += K^T . dS^T) and dK/dV kernel (a lane owns one key: S = Q . K^T, dV^T += dO^T . P,
 // dP = dO . V^T, dK^T += Q^T . dS).  P and dS are rounded to bf16 for the second GEMMs (as every flash attention does);
 // all accumulation and the softmax are fp32.
-#include "salun_common.h"
+#include "salun_device.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef s16x4 __attribute__((address_space(3))) * lds_s16x4_ptr;
-
-__device__ __forceinline__ uint16_t f2bf(float f) { return __builtin_bit_cast(uint16_t, (__bf16)f); }  // v_cvt_pk_bf16_f32: RNE
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-  bf16x2_t v;
-  v[0] = (__bf16)a; v[1] = (__bf16)b;
-  return __builtin_bit_cast(uint32_t, v);
-}
-__device__ __forceinline__ float bf2f(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
-
-__device__ __forceinline__ bf16x8 tr_operand(const char *lds_base, uint32_t byte_off, int second) {
-  lds_s16x4_ptr p0 = (lds_s16x4_ptr)(lds_base + byte_off);
-  lds_s16x4_ptr p1 = (lds_s16x4_ptr)(lds_base + byte_off + second);
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(p0);
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(p1);
-  union { struct { s16x4 a, b; } s; bf16x8 v; } u;
-  u.s.a = lo; u.s.b = hi;
-  return u.v;
-}
 // 8 fp32 -> one bf16x8 operand (element i = f[i])
 __device__ __forceinline__ bf16x8 pack_operand(const float *f) {
   union { uint32_t w[4]; bf16x8 v; } u;
@@ -490,25 +467,10 @@ int launch_bwd(const AttnArgs &a, hipStream_t st) {
                      a.do_ld, a.B, a.H, a.Nq, D);
   SALUN_LAUNCH_CHECK();
   const size_t lds_q = 2 * (size_t)KT * G::ROWB + (size_t)G::NT * KT * 64;
-  static unsigned long long attr_q = 0, attr_kv = 0;  // one bit per device
-  if (!((attr_q >> salun_device_bit()) & 1ull)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(&attn_bwd_dq<D>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds_q) != hipSuccess)
-      return SALUN_EIO;
-    attr_q |= 1ull << salun_device_bit();
-  }
-  hipLaunchKernelGGL(attn_bwd_dq<D>, dim3((a.Nq + 127) / 128, a.B * a.H), dim3(256), lds_q, st, a);
-  SALUN_LAUNCH_CHECK();
+  const int rc = salun_launch_lds<attn_bwd_dq<D>>(dim3((a.Nq + 127) / 128, a.B * a.H), dim3(256), lds_q, st, a);
+  if (rc != SALUN_OK) return rc;
   const size_t lds_kv = 2 * (size_t)32 * G::ROWB + 2 * (size_t)G::NT * 32 * 64 + 2 * 32 * sizeof(float);
-  if (!((attr_kv >> salun_device_bit()) & 1ull)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(&attn_bwd_dkv<D>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds_kv) != hipSuccess)
-      return SALUN_EIO;
-    attr_kv |= 1ull << salun_device_bit();
-  }
-  hipLaunchKernelGGL(attn_bwd_dkv<D>, dim3((a.Nk + 127) / 128, a.B * a.H), dim3(256), lds_kv, st, a);
-  SALUN_LAUNCH_CHECK();
-  return SALUN_OK;
+  return salun_launch_lds<attn_bwd_dkv<D>>(dim3((a.Nk + 127) / 128, a.B * a.H), dim3(256), lds_kv, st, a);
 }
 
 bool attn_ok(int B, int H, int Nq, int Nk, int D) {

@@ -32,21 +32,16 @@
 // that draws the last ticket re-reads all B losses (device-scope loads), sums them in float64 in the fixed block order
 // and adds the total to *loss_sum, B to *count, and writes the mean to *loss_mean.  The ticket (4 bytes of `ws`) is
 // cleared by a memset ahead of the launch.
-#include "salun_common.h"
+#include "salun_device.h"
 
 namespace {
 
 constexpr int MAX_C = SALUN_CLS_HEAD_MAX_C;
 constexpr int MAX_K = SALUN_CLS_HEAD_MAX_K;
 
-__device__ __forceinline__ float wave_sum_f32(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
 // Sum over the 256 threads, valid in EVERY thread.  `lds` holds 4 floats.
 __device__ __forceinline__ float block_sum_f32(float v, float *lds) {
-  v = wave_sum_f32(v);
+  v = salun_wave_sum_lane0(v);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) lds[wave] = v;
   __syncthreads();
@@ -97,7 +92,7 @@ __global__ __launch_bounds__(SALUN_BLOCK) void k_cls_head_fwd(
       const float *wk = w + static_cast<int64_t>(k) * C;
       float acc = 0.0f;
       for (int c = lane; c < C; c += 64) acc = fmaf(pool_s[c], wk[c], acc);
-      acc = wave_sum_f32(acc);
+      acc = salun_wave_sum_lane0(acc);
       if (lane == 0) {
         const float l = acc + bias[k];
         logit_s[k] = l;
@@ -286,7 +281,7 @@ __global__ __launch_bounds__(SALUN_BLOCK) void k_cls_head_eval(
       const float *wk = w + static_cast<int64_t>(k) * C;
       float acc = 0.0f;
       for (int c = lane; c < C; c += 64) acc = fmaf(pool_s[c], wk[c], acc);
-      acc = wave_sum_f32(acc);
+      acc = salun_wave_sum_lane0(acc);
       if (lane == 0) {
         const float l = acc + bias[k];
         logit_s[k] = l;

@@ -29,7 +29,7 @@ static inline int salun_grid_for(int64_t work_items, int per_block) {
   return static_cast<int>(b);
 }
 
-// Bit index of the calling thread's current device.  hipFuncSetAttribute's dynamic-LDS opt-in is per DEVICE: "done
+// Bit index of the calling thread's current device.  The dynamic-LDS opt-in below is per DEVICE: "done
 // once" flags are kept as one bit per device so a process that drives several GPUs configures each of them.
 static inline int salun_device_bit() {
   int dev = 0;
@@ -38,12 +38,44 @@ static inline int salun_device_bit() {
 }
 // "Done once per device" flags (dynamic-LDS opt-ins): one bit per device, read and published atomically (one host
 // thread per GPU makes a plain read-modify-write a data race).  The bit is published AFTER the work, so a racing thread
-// either repeats the (idempotent) attribute call or sees it done — never launches ahead of it.
+// either repeats the (idempotent) attribute call or sees it done — never launches ahead of it.  Every opt-in of the
+// library is salun_allow_lds below, so none keeps once-bits of its own that bypass these two functions.
 static inline bool salun_once_needed(const unsigned long long *done) {
   return ((__atomic_load_n(done, __ATOMIC_ACQUIRE) >> salun_device_bit()) & 1ull) == 0;
 }
 static inline void salun_once_mark(unsigned long long *done) {
   (void)__atomic_fetch_or(done, 1ull << salun_device_bit(), __ATOMIC_RELEASE);
+}
+
+// ---- dynamic LDS above the default limit -----------------------------------------
+// A launch with more dynamic LDS than the default limit needs a per-kernel, per-device opt-in.  The attribute call is a
+// slow driver round trip, so it is made once per kernel instantiation and device (the once-bits live in this function's
+// instantiation), and only by launches that need it: 48 KiB and less fits every default.  It asks for the device's
+// ceiling, not for `lds`: one instantiation is launched with plan-dependent sizes, and the attribute is a permission,
+// not an allocation.  The ceiling is the CU's 160 KiB less the kernel's static LDS (in whole KiB, which also covers
+// the padding in front of an aligned dynamic array): the runtime refuses a request that does not fit beside it
+// (measured on k_fullscan, the one such kernel that has static LDS).  The library sets that attribute nowhere else.
+constexpr size_t SALUN_LDS_DEFAULT = 48 * 1024;
+constexpr size_t SALUN_LDS_PER_CU = 160 * 1024;
+template <auto Kernel>
+int salun_allow_lds(size_t lds) {
+  static unsigned long long configured = 0;  // one bit per device
+  if (lds <= SALUN_LDS_DEFAULT || !salun_once_needed(&configured)) return SALUN_OK;
+  const void *fn = reinterpret_cast<const void *>(Kernel);
+  hipFuncAttributes fa;
+  if (hipFuncGetAttributes(&fa, fn) != hipSuccess) return SALUN_EIO;
+  const size_t ceiling = SALUN_LDS_PER_CU - ((fa.sharedSizeBytes + 1023) & ~size_t(1023));
+  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ceiling) != hipSuccess) return SALUN_EIO;
+  salun_once_mark(&configured);
+  return SALUN_OK;
+}
+// The opt-in, the launch, the launch check.
+template <auto Kernel, typename... Args>
+int salun_launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args &...args) {
+  if (salun_allow_lds<Kernel>(lds) != SALUN_OK) return SALUN_EIO;
+  hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
+  SALUN_LAUNCH_CHECK();
+  return SALUN_OK;
 }
 
 static inline bool salun_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }

@@ -26,11 +26,9 @@
 //   (deterministic, no float atomics); staging interleaved between the MFMAs (see the kernel).  `conv_wgrad_smallc`
 //   serves C*R*R <= 32 (the RGB stem) with the (c,r,s) combinations as the MFMA columns.
 // Ceilings (tools/micro/mfma_peak.hip): 155.6 TFLOP/s register operands, 144 with this file's LDS operand pattern.
-#include "salun_common.h"
+#include "salun_device.h"
 #include "salun_conv_plan.h"
-#include <mutex>
 #include <type_traits>
-#include <unordered_set>
 
 // salun_conv_ring.hip: the LDS-DMA ring form of the 3x3 / stride 1 / pad 1 backward-weight; refuses (SALUN_EINVAL)
 // exactly where salun_ring_wgrad_fits (salun_conv_plan.h) does
@@ -38,8 +36,6 @@ int salun_ring_wgrad_launch(const float *x, const float *dy, float *part, int N,
                             int nchunks, hipStream_t st);
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // One staged patch position of a thread: where it comes from in a channel plane and where it goes in LDS.
 struct PatchPos {
@@ -96,9 +92,8 @@ __device__ __forceinline__ void patch_pos(PatchPos &p, int e, int PSZ, int IH_t,
   }
 }
 
-// Epilogue: D[row = channel][col = pixel]; accumulator element v of a lane is row (v&3) + 8*(v>>2) (+ 4*hi, in kbase).
-__device__ __forceinline__ constexpr int acc_row(int v) { return (v & 3) + 8 * (v >> 2); }
-// The same row clamped into the tensor (klast = last real row relative to kbase): epilogue loads are unconditional — a
+// Epilogue: D[row = channel][col = pixel]; accumulator element v of a lane is row acc_row(v) (+ 4*hi, in kbase).
+// That row clamped into the tensor (klast = last real row relative to kbase): epilogue loads are unconditional — a
 // load behind a per-lane test becomes a branch with its own wait — so a row past the last channel re-reads the last one.
 __device__ __forceinline__ int acc_row_clamped(int v, int klast, int kbase) {
   return max(min(acc_row(v), klast), -kbase);
@@ -1427,7 +1422,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_smallc(const float *__restrict
 // split of a 512x512 layer 9,216 workgroups x 1 load — always thousands of 16-byte loads in flight, which the
 // round-2 kernel (4-byte loads, 32 outputs per workgroup, half its threads idle when nsplit < 8) did not have.
 // Deterministic: the summation order depends only on (nsplit, G).
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 ldg_stream4(const float4 *p) {  // one 16-byte load, streamed past the caches
   const f32x4v v = __builtin_nontemporal_load(reinterpret_cast<const f32x4v *>(p));
   return make_float4(v.x, v.y, v.z, v.w);
@@ -1579,35 +1573,22 @@ inline void launch_wgrad_reduce(const float *part, float *dw, int64_t n, int nsp
 }
 
 // ===================================================================================== host side
-// A call is planned by a pure function of its shape (salun_conv_plan.h), then launched from the plan here.
+// A call is planned by a pure function of its shape (salun_conv_plan.h), then launched from the plan here; the kernels
+// with plan-dependent dynamic LDS go through salun_launch_lds (salun_common.h).
 
-// dynamic LDS above the default limit needs a per-kernel opt-in; the attribute call is a slow driver round trip,
-// so it is made once per kernel (process-wide table, the only mutable global state of the library).
-inline void allow_lds_once(const void *fn) {
-  static std::mutex mu;
-  static std::unordered_set<uintptr_t> done;  // (kernel, device): the opt-in is per device
-  std::lock_guard<std::mutex> lk(mu);
-  if (done.insert(reinterpret_cast<uintptr_t>(fn) ^ ((uintptr_t)(salun_device_bit() + 1) << 56)).second)
-    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-}
-template <typename F>
-inline void allow_lds(F fn, size_t bytes) {
-  if (bytes > 48 * 1024) allow_lds_once(reinterpret_cast<const void *>(fn));
-}
-
-// f(KT, WP, WK) with the tile's wave grid as compile-time constants: the five shapes pick_tile / pick_tile_s2 produce
+// f(KT, WP, WK) with the tile's wave grid as compile-time constants: the five shapes pick_tile / pick_tile_s2 produce.
+// Returns what f returns (the launch's status).
 template <int V>
 using ic = std::integral_constant<int, V>;
 template <typename F>
-inline void with_tile(const Tile &t, F &&f) {
+inline int with_tile(const Tile &t, F &&f) {
   if (t.WP == 4) {
-    if (t.KT == 4) f(ic<4>{}, ic<4>{}, ic<1>{});
-    else if (t.KT == 2) f(ic<2>{}, ic<4>{}, ic<1>{});
-    else f(ic<1>{}, ic<4>{}, ic<1>{});
-  } else {
-    if (t.KT == 2) f(ic<2>{}, ic<2>{}, ic<2>{});
-    else f(ic<1>{}, ic<2>{}, ic<2>{});
+    if (t.KT == 4) return f(ic<4>{}, ic<4>{}, ic<1>{});
+    if (t.KT == 2) return f(ic<2>{}, ic<4>{}, ic<1>{});
+    return f(ic<1>{}, ic<4>{}, ic<1>{});
   }
+  if (t.KT == 2) return f(ic<2>{}, ic<2>{}, ic<2>{});
+  return f(ic<1>{}, ic<2>{}, ic<2>{});
 }
 
 // Second half of a reduction-split launch: y = sum_z part[z] (fixed order) + the epilogue terms the split workgroups
@@ -1639,37 +1620,38 @@ struct DataArgs {
 };
 
 template <int R, int STRIDE, int KT, int WP, int WK, bool DGRAD, bool FAST, int PT, bool SPLIT, bool EPI>
-void launch_one_igemm(const DataPlan &p, const DataArgs &a, hipStream_t st) {
+int launch_one_igemm(const DataPlan &p, const DataArgs &a, hipStream_t st) {
   const TileGeom &g = p.t.g;
   const dim3 grid(g.ntiles, p.wgs / g.ntiles, SPLIT ? p.S : 1);
-  allow_lds(conv_igemm<R, STRIDE, KT, WP, WK, DGRAD, FAST, PT, SPLIT, EPI>, p.lds_bytes);
   // a reduction share writes a partial image and leaves every epilogue term to conv_split_finish
-  hipLaunchKernelGGL((conv_igemm<R, STRIDE, KT, WP, WK, DGRAD, FAST, PT, SPLIT, EPI>), grid, dim3(256), p.lds_bytes, st,
-                     a.x, a.w, SPLIT ? nullptr : a.bias, SPLIT ? a.part : a.y, a.N, a.xC, a.xH, a.xW, a.yC, a.yH, a.yW,
-                     a.pad, g.NI, g.TP, g.IH_t, g.IW_t, g.logQ, a.wC, a.wK, EPI ? a.nbias : nullptr,
-                     EPI ? a.addend : nullptr, SPLIT ? a.xC / p.S : 0);
+  return salun_launch_lds<conv_igemm<R, STRIDE, KT, WP, WK, DGRAD, FAST, PT, SPLIT, EPI>>(
+      grid, dim3(256), p.lds_bytes, st, a.x, a.w, SPLIT ? nullptr : a.bias, SPLIT ? a.part : a.y, a.N, a.xC, a.xH, a.xW,
+      a.yC, a.yH, a.yW, a.pad, g.NI, g.TP, g.IH_t, g.IW_t, g.logQ, a.wC, a.wK, EPI ? a.nbias : nullptr,
+      EPI ? a.addend : nullptr, SPLIT ? a.xC / p.S : 0);
 }
 
 template <int R, int STRIDE, bool DGRAD>
 int launch_data(const DataPlan &p, const DataArgs &a, hipStream_t st) {
+  int rc = SALUN_OK;
   if (p.t.PT == 2) {
-    launch_one_igemm<R, STRIDE, 2, 4, 1, DGRAD, true, 2, false, false>(p, a, st);
+    rc = launch_one_igemm<R, STRIDE, 2, 4, 1, DGRAD, true, 2, false, false>(p, a, st);
   } else {
-    with_tile(p.t, [&](auto kt, auto wp, auto wk) {
+    rc = with_tile(p.t, [&](auto kt, auto wp, auto wk) {
       constexpr int KT = decltype(kt)::value, WP = decltype(wp)::value, WK = decltype(wk)::value;
       constexpr bool CAN_SPLIT = (WP == 2 && KT == 1), CAN_EPI = (!DGRAD && STRIDE == 1);  // as plan_data grants them
       if (!p.fast) {
-        launch_one_igemm<R, STRIDE, KT, WP, WK, DGRAD, false, 1, false, false>(p, a, st);
+        return launch_one_igemm<R, STRIDE, KT, WP, WK, DGRAD, false, 1, false, false>(p, a, st);
       } else if (p.S > 1) {
-        if constexpr (CAN_SPLIT) launch_one_igemm<R, STRIDE, KT, WP, WK, DGRAD, true, 1, true, false>(p, a, st);
+        if constexpr (CAN_SPLIT) return launch_one_igemm<R, STRIDE, KT, WP, WK, DGRAD, true, 1, true, false>(p, a, st);
       } else if (p.epi) {
-        if constexpr (CAN_EPI) launch_one_igemm<R, STRIDE, KT, WP, WK, DGRAD, true, 1, false, true>(p, a, st);
+        if constexpr (CAN_EPI) return launch_one_igemm<R, STRIDE, KT, WP, WK, DGRAD, true, 1, false, true>(p, a, st);
       } else {
-        launch_one_igemm<R, STRIDE, KT, WP, WK, DGRAD, true, 1, false, false>(p, a, st);
+        return launch_one_igemm<R, STRIDE, KT, WP, WK, DGRAD, true, 1, false, false>(p, a, st);
       }
+      return (int)SALUN_OK;
     });
   }
-  SALUN_LAUNCH_CHECK();
+  if (rc != SALUN_OK) return rc;
   if (p.S > 1) {
     hipLaunchKernelGGL(conv_split_finish, dim3((unsigned)((p.out_elems / 4 + 255) / 256)), dim3(256), 0, st, a.part, p.S,
                        p.out_elems, DGRAD ? nullptr : a.bias, a.nbias, a.addend, DGRAD ? a.bias : nullptr, a.y, a.yC,
@@ -1687,34 +1669,32 @@ inline int launch_data(const DataPlan &p, const DataArgs &a, hipStream_t st) {
 }
 
 template <int R, int PAD, int KT, int WP, int WK>
-void launch_one_dgrad_s2(const Dgrad2Plan &p, const float *dy, const float *w, const float *addend, float *dx, int N,
-                         int C, int H, int W, int K, int P, int Q, hipStream_t st) {
+int launch_one_dgrad_s2(const Dgrad2Plan &p, const float *dy, const float *w, const float *addend, float *dx, int N,
+                        int C, int H, int W, int K, int P, int Q, hipStream_t st) {
   const TileGeom &g = p.t.g;
-  allow_lds(conv_dgrad_s2<R, PAD, KT, WP, WK>, p.lds_bytes);
-  hipLaunchKernelGGL((conv_dgrad_s2<R, PAD, KT, WP, WK>), dim3(g.ntiles, C / p.t.kb()), dim3(256), p.lds_bytes, st, dy, w,
-                     addend, dx, N, K, P, Q, C, H, W, g.NI, g.TP, g.IH_t, g.IW_t, g.logQ);
+  return salun_launch_lds<conv_dgrad_s2<R, PAD, KT, WP, WK>>(dim3(g.ntiles, C / p.t.kb()), dim3(256), p.lds_bytes, st, dy,
+                                                             w, addend, dx, N, K, P, Q, C, H, W, g.NI, g.TP, g.IH_t,
+                                                             g.IW_t, g.logQ);
 }
 
 template <int RH, int RW, int KT, int WP, int WK, int MAXPOS>
-void launch_one_dgrad_tap(const TapClass &c, const TapArgs &a, hipStream_t st) {
-  allow_lds(conv_dgrad_tap<RH, RW, KT, WP, WK, MAXPOS>, c.lds_bytes);
-  hipLaunchKernelGGL((conv_dgrad_tap<RH, RW, KT, WP, WK, MAXPOS>), dim3(c.t.g.ntiles, (a.yC + c.t.kb() - 1) / c.t.kb()),
-                     dim3(256), c.lds_bytes, st, a);
+int launch_one_dgrad_tap(const TapClass &c, const TapArgs &a, hipStream_t st) {
+  return salun_launch_lds<conv_dgrad_tap<RH, RW, KT, WP, WK, MAXPOS>>(
+      dim3(c.t.g.ntiles, (a.yC + c.t.kb() - 1) / c.t.kb()), dim3(256), c.lds_bytes, st, a);
 }
 
 inline int launch_dgrad_s2(const Dgrad2Plan &p, const float *dy, const float *w, const float *addend, float *dx, int N,
                            int C, int H, int W, int K, int P, int Q, hipStream_t st) {
   if (p.merged) {
-    with_tile(p.t, [&](auto kt, auto wp, auto wk) {
+    return with_tile(p.t, [&](auto kt, auto wp, auto wk) {
       constexpr int KT = decltype(kt)::value, WP = decltype(wp)::value, WK = decltype(wk)::value;
       if constexpr (KT <= 2) {  // pick_tile_s2
-        if (p.R == 1) launch_one_dgrad_s2<1, 0, KT, WP, WK>(p, dy, w, addend, dx, N, C, H, W, K, P, Q, st);
-        else if (p.pad == 1) launch_one_dgrad_s2<3, 1, KT, WP, WK>(p, dy, w, addend, dx, N, C, H, W, K, P, Q, st);
-        else launch_one_dgrad_s2<3, 0, KT, WP, WK>(p, dy, w, addend, dx, N, C, H, W, K, P, Q, st);
+        if (p.R == 1) return launch_one_dgrad_s2<1, 0, KT, WP, WK>(p, dy, w, addend, dx, N, C, H, W, K, P, Q, st);
+        if (p.pad == 1) return launch_one_dgrad_s2<3, 1, KT, WP, WK>(p, dy, w, addend, dx, N, C, H, W, K, P, Q, st);
+        return launch_one_dgrad_s2<3, 0, KT, WP, WK>(p, dy, w, addend, dx, N, C, H, W, K, P, Q, st);
       }
+      return (int)SALUN_OK;
     });
-    SALUN_LAUNCH_CHECK();
-    return SALUN_OK;
   }
   TapArgs a{};
   a.x = dy; a.w = w; a.bias = addend; a.y = dx;
@@ -1736,19 +1716,19 @@ inline int launch_dgrad_s2(const Dgrad2Plan &p, const float *dy, const float *w,
     a.ph = c.ph; a.pw = c.pw;
     a.rtop_h = c.rtop_h; a.rtop_w = c.rtop_w; a.vpad_h = c.vpad_h; a.vpad_w = c.vpad_w;
     a.NI = g.NI; a.TP = g.TP; a.IH_t = g.IH_t; a.IW_t = g.IW_t; a.logQ = g.logQ;
-    with_tile(c.t, [&](auto kt, auto wp, auto wk) {
+    const int rc = with_tile(c.t, [&](auto kt, auto wp, auto wk) {
       constexpr int KT = decltype(kt)::value, WP = decltype(wp)::value, WK = decltype(wk)::value;
       auto taps = [&](auto rh, auto rw) {
         constexpr int RH = decltype(rh)::value, RW = decltype(rw)::value;
-        if (c.maxpos == 1) launch_one_dgrad_tap<RH, RW, KT, WP, WK, 1>(c, a, st);
-        else launch_one_dgrad_tap<RH, RW, KT, WP, WK, 3>(c, a, st);
+        if (c.maxpos == 1) return launch_one_dgrad_tap<RH, RW, KT, WP, WK, 1>(c, a, st);
+        return launch_one_dgrad_tap<RH, RW, KT, WP, WK, 3>(c, a, st);
       };
-      if (c.RH == 1 && c.RW == 1) taps(ic<1>{}, ic<1>{});
-      else if (c.RH == 1) taps(ic<1>{}, ic<2>{});
-      else if (c.RW == 1) taps(ic<2>{}, ic<1>{});
-      else taps(ic<2>{}, ic<2>{});
+      if (c.RH == 1 && c.RW == 1) return taps(ic<1>{}, ic<1>{});
+      if (c.RH == 1) return taps(ic<1>{}, ic<2>{});
+      if (c.RW == 1) return taps(ic<2>{}, ic<1>{});
+      return taps(ic<2>{}, ic<2>{});
     });
-    SALUN_LAUNCH_CHECK();
+    if (rc != SALUN_OK) return rc;
   }
   return SALUN_OK;
 }
@@ -1760,67 +1740,64 @@ struct WgradArgs {
 };
 
 template <int STRIDE>
-void launch_one_wgrad_1x1(const WgradPlan &p, const WgradArgs &a, hipStream_t st) {
-  allow_lds(conv_wgrad_1x1<STRIDE>, p.lds_bytes);
-  hipLaunchKernelGGL(conv_wgrad_1x1<STRIDE>, dim3((a.K + 127) / 128, (a.C + 127) / 128, p.gz), dim3(256), p.lds_bytes, st,
-                     a.x, a.dy, a.part, a.N, a.C, a.H, a.W, a.K, a.P, a.Q, p.nchunks);
+int launch_one_wgrad_1x1(const WgradPlan &p, const WgradArgs &a, hipStream_t st) {
+  return salun_launch_lds<conv_wgrad_1x1<STRIDE>>(dim3((a.K + 127) / 128, (a.C + 127) / 128, p.gz), dim3(256), p.lds_bytes,
+                                                  st, a.x, a.dy, a.part, a.N, a.C, a.H, a.W, a.K, a.P, a.Q, p.nchunks);
 }
 template <int R, int STRIDE>
-void launch_one_wgrad_smallc(const WgradPlan &p, const WgradArgs &a, hipStream_t st) {
+int launch_one_wgrad_smallc(const WgradPlan &p, const WgradArgs &a, hipStream_t st) {
   const TileGeom &g = p.g;
   hipLaunchKernelGGL((conv_wgrad_smallc<R, STRIDE>), dim3((a.K + 63) / 64, 1, p.gz), dim3(256), p.lds_bytes, st, a.x, a.dy,
                      a.part, a.N, a.C, a.H, a.W, a.K, a.P, a.Q, a.pad, g.NI, g.TP, g.IH_t, g.IW_t, g.logQ, g.ntiles);
+  SALUN_LAUNCH_CHECK();
+  return SALUN_OK;
 }
 template <int STRIDE, int NIT>
-void launch_one_wgrad_v(const WgradPlan &p, const WgradArgs &a, hipStream_t st) {
+int launch_one_wgrad_v(const WgradPlan &p, const WgradArgs &a, hipStream_t st) {
   const TileGeom &g = p.g;
-  allow_lds(conv_wgrad_v<STRIDE, NIT>, p.lds_bytes);
-  hipLaunchKernelGGL((conv_wgrad_v<STRIDE, NIT>), dim3((a.K + 63) / 64, (a.C + 63) / 64, p.gz), dim3(256), p.lds_bytes, st,
-                     a.x, a.dy, a.part, a.N, a.C, a.H, a.W, a.K, a.P, a.Q, g.NI, g.TP, g.IH_t, g.IW_t, g.logQ, g.ntiles);
+  return salun_launch_lds<conv_wgrad_v<STRIDE, NIT>>(dim3((a.K + 63) / 64, (a.C + 63) / 64, p.gz), dim3(256), p.lds_bytes,
+                                                     st, a.x, a.dy, a.part, a.N, a.C, a.H, a.W, a.K, a.P, a.Q, g.NI, g.TP,
+                                                     g.IH_t, g.IW_t, g.logQ, g.ntiles);
 }
 template <int R, int STRIDE, bool FULLC>
-void launch_one_wgrad(const WgradPlan &p, const WgradArgs &a, hipStream_t st) {
+int launch_one_wgrad(const WgradPlan &p, const WgradArgs &a, hipStream_t st) {
   const TileGeom &g = p.g;
-  allow_lds(conv_wgrad<R, STRIDE, FULLC>, p.lds_bytes);
-  hipLaunchKernelGGL((conv_wgrad<R, STRIDE, FULLC>), dim3((a.K + 63) / 64, (a.C + 63) / 64, p.gz), dim3(256), p.lds_bytes,
-                     st, a.x, a.dy, a.part, a.N, a.C, a.H, a.W, a.K, a.P, a.Q, a.pad, g.NI, g.TP, g.IH_t, g.IW_t, g.logQ,
-                     g.ntiles);
+  return salun_launch_lds<conv_wgrad<R, STRIDE, FULLC>>(dim3((a.K + 63) / 64, (a.C + 63) / 64, p.gz), dim3(256),
+                                                        p.lds_bytes, st, a.x, a.dy, a.part, a.N, a.C, a.H, a.W, a.K, a.P,
+                                                        a.Q, a.pad, g.NI, g.TP, g.IH_t, g.IW_t, g.logQ, g.ntiles);
 }
 
-// f(R, STRIDE) as compile-time constants
+// f(R, STRIDE) as compile-time constants; returns what f returns
 template <typename F>
-inline void with_filter(int R, int stride, F &&f) {
-  if (R == 3) { if (stride == 1) f(ic<3>{}, ic<1>{}); else f(ic<3>{}, ic<2>{}); }
-  else { if (stride == 1) f(ic<1>{}, ic<1>{}); else f(ic<1>{}, ic<2>{}); }
+inline int with_filter(int R, int stride, F &&f) {
+  if (R == 3) return stride == 1 ? f(ic<3>{}, ic<1>{}) : f(ic<3>{}, ic<2>{});
+  return stride == 1 ? f(ic<1>{}, ic<1>{}) : f(ic<1>{}, ic<2>{});
 }
 
 // the partial sums of a planned backward-weight call (the reduce kernel follows)
 inline int launch_wgrad(const WgradPlan &p, const WgradArgs &a, hipStream_t st) {
   switch (p.route) {
     case WG_1X1:
-      if (p.stride == 1) launch_one_wgrad_1x1<1>(p, a, st);
-      else launch_one_wgrad_1x1<2>(p, a, st);
-      break;
+      return p.stride == 1 ? launch_one_wgrad_1x1<1>(p, a, st) : launch_one_wgrad_1x1<2>(p, a, st);
     case WG_SMALLC:
-      with_filter(p.R, p.stride, [&](auto r, auto s) { launch_one_wgrad_smallc<decltype(r)::value, decltype(s)::value>(p, a, st); });
-      break;
+      return with_filter(p.R, p.stride, [&](auto r, auto s) {
+        return launch_one_wgrad_smallc<decltype(r)::value, decltype(s)::value>(p, a, st);
+      });
     case WG_RING:
       return salun_ring_wgrad_launch(a.x, a.dy, a.part, a.N, a.C, a.H, a.W, a.K, p.gz, p.nchunks, st);
     case WG_V:
       switch (p.stride * 100 + p.nit) {
-        case 105: launch_one_wgrad_v<1, 5>(p, a, st); break;
-        case 106: launch_one_wgrad_v<1, 6>(p, a, st); break;
-        case 108: launch_one_wgrad_v<1, 8>(p, a, st); break;
-        case 209: launch_one_wgrad_v<2, 9>(p, a, st); break;
-        default: launch_one_wgrad_v<2, 10>(p, a, st); break;
+        case 105: return launch_one_wgrad_v<1, 5>(p, a, st);
+        case 106: return launch_one_wgrad_v<1, 6>(p, a, st);
+        case 108: return launch_one_wgrad_v<1, 8>(p, a, st);
+        case 209: return launch_one_wgrad_v<2, 9>(p, a, st);
+        default: return launch_one_wgrad_v<2, 10>(p, a, st);
       }
-      break;
     case WG_GENERAL:
-      with_filter(p.R, p.stride, [&](auto r, auto s) {
-        if (p.fullC) launch_one_wgrad<decltype(r)::value, decltype(s)::value, true>(p, a, st);
-        else launch_one_wgrad<decltype(r)::value, decltype(s)::value, false>(p, a, st);
+      return with_filter(p.R, p.stride, [&](auto r, auto s) {
+        if (p.fullC) return launch_one_wgrad<decltype(r)::value, decltype(s)::value, true>(p, a, st);
+        return launch_one_wgrad<decltype(r)::value, decltype(s)::value, false>(p, a, st);
       });
-      break;
   }
   SALUN_LAUNCH_CHECK();
   return SALUN_OK;

@@ -27,34 +27,7 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef s16x4 __attribute__((address_space(3))) * lds_s16x4_ptr;
-
-// round-to-nearest-even, NaN -> quiet NaN (what torch's float -> bfloat16 does)
-__device__ __forceinline__ uint16_t f2bf(float f) { return __builtin_bit_cast(uint16_t, (__bf16)f); }  // v_cvt_pk_bf16_f32: RNE
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-  bf16x2_t v;
-  v[0] = (__bf16)a; v[1] = (__bf16)b;
-  return __builtin_bit_cast(uint32_t, v);
-}
-__device__ __forceinline__ float bf2f(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
-
-// 8 bf16 (one MFMA operand) = two transposing reads of 4: lane i of a 16-lane group receives column i of the
-// [4 rows][16 columns] block its group addresses (probe: tools/micro/bf16_probe.hip); `second` is the byte distance
-// of rows +4.
-__device__ __forceinline__ bf16x8 tr_operand(const char *lds_base, uint32_t byte_off, int second) {
-  lds_s16x4_ptr p0 = (lds_s16x4_ptr)(lds_base + byte_off);
-  lds_s16x4_ptr p1 = (lds_s16x4_ptr)(lds_base + byte_off + second);
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(p0);
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(p1);
-  union { struct { s16x4 a, b; } s; bf16x8 v; } u;
-  u.s.a = lo; u.s.b = hi;
-  return u.v;
-}
 
 // ------------------------------------------------------------------------------------------------ pack
 // fp32 OIHW [K][C][RS] -> bf16 [K][RS][C]; one thread writes 8 consecutive channels (16 B).
@@ -261,7 +234,6 @@ void conv_bf16_igemm(const IgArgs g) {
   int ls = st_begin, ltap = st_begin / cchunks, lc0 = (st_begin - ltap * cchunks) * BK;
   bool lneed = true;
   uint32_t wu_prev = 0;
-  typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
   auto ld128 = [&](const __amdgpu_buffer_rsrc_t &rs, uint32_t voff, uint32_t soff) {
     const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 0);
     return make_uint4(v.x, v.y, v.z, v.w);
@@ -507,7 +479,6 @@ __global__ __launch_bounds__(256, (R == 3 && ST == 1) ? 2 : 1) void conv_bf16_wg
   const __amdgpu_buffer_rsrc_t rdyb = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(g.dy), 0, (int)g.dy_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rxb = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(g.x), 0, (int)g.x_bytes, 0x00020000);
   constexpr uint32_t OOB = 0x80000000u;  // past the end of either tensor (the launcher refuses >= 2^31 bytes)
-  typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
   auto ld128 = [&](const __amdgpu_buffer_rsrc_t &rs, uint32_t voff, uint32_t soff) {
     const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 0);
     return make_uint4(v.x, v.y, v.z, v.w);
@@ -832,8 +803,8 @@ int launch_igemm(const ConvDataPlan &p, IgArgs a, void *ws, hipStream_t st) {
   a.part = p.splits > 1 ? static_cast<float *>(ws) : nullptr;
   a.x_bytes = p.x_bytes;
   a.w_bytes = p.w_bytes;
-  const int rc = launch_lds<conv_bf16_igemm<WM, WN, BK, BTR>>(dim3(p.mt, p.nt, p.splits), dim3(64 * WM * WN),
-                                                              2 * (size_t)(A_BYTES + B_BYTES), st, a);
+  const int rc = salun_launch_lds<conv_bf16_igemm<WM, WN, BK, BTR>>(dim3(p.mt, p.nt, p.splits), dim3(64 * WM * WN),
+                                                                    2 * (size_t)(A_BYTES + B_BYTES), st, a);
   if (rc != SALUN_OK) return rc;
   if (p.splits > 1) {
     const int64_t total = (int64_t)a.M * (a.Kout / 8);
@@ -859,8 +830,8 @@ int dispatch_igemm(const ConvDataPlan &p, const IgArgs &a, void *ws, hipStream_t
 template <int R, int ST>
 int launch_wgrad(const WgArgs &a, int splits, hipStream_t st) {
   constexpr int PW = 7 * ST + R;
-  return launch_lds<conv_bf16_wgrad<R, ST>>(dim3((a.K + 63) / 64, (a.C + 63) / 64, splits), dim3(256),
-                                            2 * (size_t)(2 * 64 * 64 + 2 * PW * PW * 64), st, a);
+  return salun_launch_lds<conv_bf16_wgrad<R, ST>>(dim3((a.K + 63) / 64, (a.C + 63) / 64, splits), dim3(256),
+                                                  2 * (size_t)(2 * 64 * 64 + 2 * PW * PW * 64), st, a);
 }
 
 }  // namespace

@@ -36,13 +36,11 @@
 //   o = acc;  o = o * scale[k];  o = o + shift[k];  o = o + addend;  o = o < 0 ? 0 : o.
 // No atomics, no workspace: an element's bits depend on its own reduction only, not on the tile, the batch or the run.
 // Indexing is 64-bit wherever a tensor offset is formed.
-#include "salun_common.h"
+#include "salun_device.h"
 #include <stdio.h>
 #include <string.h>
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int CC = 16;  // reduction products per stage
 
@@ -54,8 +52,6 @@ struct InferArgs {
   long long npq;  // N * P * Q
   int nkt;        // channel tiles
 };
-
-__device__ __forceinline__ constexpr int acc_row(int v) { return (v & 3) + 8 * (v >> 2); }
 
 template <int PB, int KB, bool GENERIC>
 __global__ __launch_bounds__(256) void conv_infer(const InferArgs g) {

@@ -22,14 +22,12 @@
 //     prologue per tile.
 // Numerics: exact fp32 FMA chains like conv_igemm; the summation order over (channel, tap) inside a chunk differs
 // (k-steps pair channels (2i, 2i+1) as before, in the same order), results are bit-identical to conv_igemm's.
-#include "salun_common.h"
+#include "salun_device.h"
 #include <mutex>
 #include <type_traits>
-#include <unordered_set>
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __attribute__((address_space(3))) char *ring_lds_ptr_t;
 
 constexpr int RCC = 8;      // reduction channels per chunk
@@ -490,7 +488,6 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_ring(const WgradRingArgs g)
           // 4 x odd floats is a 4-way bank conflict (64 % of this kernel's LDS cycles in the first build:
           // profiles/r06_conv_sq_*), the 16-byte read is conflict-free like the operand's own
           // (volatile: hipcc narrows a 16-byte load of which one element is used back to the conflicting dword read)
-          typedef float f32x4v __attribute__((ext_vector_type(4)));
           typedef const volatile __attribute__((address_space(3))) f32x4v *lds_v4_t;  // (explicitly LDS: a volatile
           const f32x4v lv = *(lds_v4_t)(ring_lds_ptr_t)(B + off - 16);                 //  generic pointer loads flat)
           const f32x4v rv = *(lds_v4_t)(ring_lds_ptr_t)(B + off + 16);
@@ -565,14 +562,6 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_ring(const WgradRingArgs g)
     }
 }
 
-inline void ring_allow_lds(const void *fn) {
-  static std::mutex mu;
-  static std::unordered_set<uintptr_t> done;
-  std::lock_guard<std::mutex> lk(mu);
-  if (done.insert(reinterpret_cast<uintptr_t>(fn) ^ ((uintptr_t)(salun_device_bit() + 1) << 56)).second)
-    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-}
-
 // device address of the page of zeros (per device, looked up once)
 inline const float *ring_zero_page() {
   static const float *page[64] = {nullptr};
@@ -643,15 +632,8 @@ int ring_launch(RingArgs a, int W, bool epi, int wgs_per_cu, hipStream_t st) {
   if (ldsb > 80 * 1024) return SALUN_EINVAL;  // two workgroups per CU
   int grid = wgs_per_cu * ring_cu_count();
   if (grid > a.ntiles) grid = a.ntiles;
-  if (epi) {
-    ring_allow_lds(reinterpret_cast<const void *>(conv3x3_ring<LOGW, PT, KT, WP, WK, true>));
-    hipLaunchKernelGGL((conv3x3_ring<LOGW, PT, KT, WP, WK, true>), dim3(grid), dim3(256), ldsb, st, a);
-  } else {
-    ring_allow_lds(reinterpret_cast<const void *>(conv3x3_ring<LOGW, PT, KT, WP, WK, false>));
-    hipLaunchKernelGGL((conv3x3_ring<LOGW, PT, KT, WP, WK, false>), dim3(grid), dim3(256), ldsb, st, a);
-  }
-  SALUN_LAUNCH_CHECK();
-  return SALUN_OK;
+  if (epi) return salun_launch_lds<conv3x3_ring<LOGW, PT, KT, WP, WK, true>>(dim3(grid), dim3(256), ldsb, st, a);
+  return salun_launch_lds<conv3x3_ring<LOGW, PT, KT, WP, WK, false>>(dim3(grid), dim3(256), ldsb, st, a);
 }
 
 template <int LOGW>
@@ -693,17 +675,14 @@ int salun_ring_wgrad_launch(const float *x, const float *dy, float *part, int N,
     constexpr int W_ = 1 << LOGW, TP_ = (W_ * W_ >= 64) ? 64 / W_ : W_, NI_ = (W_ * W_ >= 64) ? 1 : 64 / (W_ * W_);
     constexpr int PRX_ = (NI_ * (TP_ + 2) * (W_ / 4)) | 1;
     const size_t ldsb = 2 * (size_t)(64 * 17 * 16 + 64 * PRX_ * 16);
-    ring_allow_lds(reinterpret_cast<const void *>(conv3x3_wgrad_ring<LOGW>));
-    hipLaunchKernelGGL((conv3x3_wgrad_ring<LOGW>), grid, dim3(256), ldsb, st, a);
+    return salun_launch_lds<conv3x3_wgrad_ring<LOGW>>(grid, dim3(256), ldsb, st, a);
   };
   switch (W) {
-    case 4: launch(std::integral_constant<int, 2>{}); break;
-    case 8: launch(std::integral_constant<int, 3>{}); break;
-    case 16: launch(std::integral_constant<int, 4>{}); break;
-    default: launch(std::integral_constant<int, 5>{}); break;
+    case 4: return launch(std::integral_constant<int, 2>{});
+    case 8: return launch(std::integral_constant<int, 3>{});
+    case 16: return launch(std::integral_constant<int, 4>{});
+    default: return launch(std::integral_constant<int, 5>{});
   }
-  SALUN_LAUNCH_CHECK();
-  return SALUN_OK;
 }
 
 SALUN_EXPORT size_t salun_conv3x3_pack_bytes(int K, int C, int dgrad) {

@@ -13,11 +13,9 @@
 //                  p = mu + sqrt(var) z in place, z = the counter-based normal of salun_fill_normal at the flat index.
 // No group sum is squared before its reduction is complete; every reduction runs in a fixed order and there are no
 // float atomics, so two launches on the same inputs give bit-identical results.
-#include "salun_common.h"
+#include "salun_device.h"
 
 namespace {
-
-inline size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
 
 // F[e] += sum_g w[g] gs[g * n + e]^2, g in increasing order, fp64      (float4 path: n % 4 == 0, all bases aligned)
 __global__ __launch_bounds__(SALUN_BLOCK) void k_ff_sq_acc4(const float *__restrict__ gs, const float *__restrict__ w,

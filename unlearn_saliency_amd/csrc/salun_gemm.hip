@@ -28,8 +28,6 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int MAXJ = SALUN_GEMM_MAX_JOBS;
 constexpr int MAXS = SALUN_GEMM_MAX_SEGS;
 constexpr int BK = 16;
@@ -304,11 +302,6 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
   return v;
 }
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 __global__ __launch_bounds__(256) void k_softmax_rows(float *__restrict__ s, long long rows, int n, int ld) {
   const int lane = threadIdx.x & 63;
@@ -323,7 +316,7 @@ __global__ __launch_bounds__(256) void k_softmax_rows(float *__restrict__ s, lon
       row[jj] = e;
       sum += e;
     }
-    sum = wave_sum(sum);
+    sum = salun_wave_sum_all(sum);
     const float inv = 1.0f / sum;
     for (int jj = lane; jj < n; jj += 64) row[jj] *= inv;
   }
@@ -338,7 +331,7 @@ __global__ __launch_bounds__(256) void k_softmax_rows_bwd(const float *__restric
     float *dr = dp + r * ld;
     float dot = 0.f;
     for (int jj = lane; jj < n; jj += 64) dot += pr[jj] * dr[jj];
-    dot = wave_sum(dot);
+    dot = salun_wave_sum_all(dot);
     for (int jj = lane; jj < n; jj += 64) dr[jj] = scale * (pr[jj] * (dr[jj] - dot));
   }
 }
@@ -622,7 +615,6 @@ SALUN_EXPORT int salun_colsum_f32(const float *x, float *out, int64_t M, int N, 
 // and are never stored).
 namespace {
 
-typedef __bf16 g_bf16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) char *lds_ptr_t;
 
 struct GbArgs {
@@ -634,15 +626,6 @@ struct GbArgs {
   int M, N, K;
   int tiles_m, tiles_n;
 };
-
-__device__ __forceinline__ uint32_t gb_pack2(float a, float b) {
-  typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-  bf2 v;
-  v[0] = (__bf16)a; v[1] = (__bf16)b;
-  return __builtin_bit_cast(uint32_t, v);
-}
-__device__ __forceinline__ float gb_lo(uint32_t u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float gb_hi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
 
 template <int WGM, int WGN, bool DB>
 __global__ __launch_bounds__(64 * WGM * WGN) void k_gemm_bf16_nt(const GbArgs g) {
@@ -716,10 +699,10 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_gemm_bf16_nt(const GbArgs g)
     const char *base = lds + buf * STAGE;
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
-      const g_bf16x8 w0 = *reinterpret_cast<const g_bf16x8 *>(base + w_row + ch[kk]);
-      const g_bf16x8 w1 = *reinterpret_cast<const g_bf16x8 *>(base + w_row + 32 * 128 + ch[kk]);
-      const g_bf16x8 x0 = *reinterpret_cast<const g_bf16x8 *>(base + x_row + ch[kk]);
-      const g_bf16x8 x1 = *reinterpret_cast<const g_bf16x8 *>(base + x_row + 32 * 128 + ch[kk]);
+      const bf16x8 w0 = *reinterpret_cast<const bf16x8 *>(base + w_row + ch[kk]);
+      const bf16x8 w1 = *reinterpret_cast<const bf16x8 *>(base + w_row + 32 * 128 + ch[kk]);
+      const bf16x8 x0 = *reinterpret_cast<const bf16x8 *>(base + x_row + ch[kk]);
+      const bf16x8 x1 = *reinterpret_cast<const bf16x8 *>(base + x_row + 32 * 128 + ch[kk]);
       acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, x0, acc[0][0], 0, 0, 0);
       acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, x1, acc[0][1], 0, 0, 0);
       acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1, x0, acc[1][0], 0, 0, 0);
@@ -764,9 +747,9 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_gemm_bf16_nt(const GbArgs g)
         const size_t e = (size_t)m * g.N + n;
         if (g.addend) {
           const uint2 av = *reinterpret_cast<const uint2 *>(g.addend + e);
-          o0 += gb_lo(av.x); o1 += gb_hi(av.x); o2 += gb_lo(av.y); o3 += gb_hi(av.y);
+          o0 += bf_lo(av.x); o1 += bf_hi(av.x); o2 += bf_lo(av.y); o3 += bf_hi(av.y);
         }
-        *reinterpret_cast<uint2 *>(g.y + e) = make_uint2(gb_pack2(o0, o1), gb_pack2(o2, o3));
+        *reinterpret_cast<uint2 *>(g.y + e) = make_uint2(pack2(o0, o1), pack2(o2, o3));
       }
   }
 }
@@ -863,10 +846,10 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_gemm_bf16_nt_p(const GbArgs 
     const char *base = lds + buf * STAGE;
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
-      const g_bf16x8 w0 = *reinterpret_cast<const g_bf16x8 *>(base + w_row + ch[kk]);
-      const g_bf16x8 w1 = *reinterpret_cast<const g_bf16x8 *>(base + w_row + 32 * 128 + ch[kk]);
-      const g_bf16x8 x0 = *reinterpret_cast<const g_bf16x8 *>(base + x_row + ch[kk]);
-      const g_bf16x8 x1 = *reinterpret_cast<const g_bf16x8 *>(base + x_row + 32 * 128 + ch[kk]);
+      const bf16x8 w0 = *reinterpret_cast<const bf16x8 *>(base + w_row + ch[kk]);
+      const bf16x8 w1 = *reinterpret_cast<const bf16x8 *>(base + w_row + 32 * 128 + ch[kk]);
+      const bf16x8 x0 = *reinterpret_cast<const bf16x8 *>(base + x_row + ch[kk]);
+      const bf16x8 x1 = *reinterpret_cast<const bf16x8 *>(base + x_row + 32 * 128 + ch[kk]);
       acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, x0, acc[0][0], 0, 0, 0);
       acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, x1, acc[0][1], 0, 0, 0);
       acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1, x0, acc[1][0], 0, 0, 0);
@@ -894,9 +877,9 @@ __global__ __launch_bounds__(64 * WGM * WGN) void k_gemm_bf16_nt_p(const GbArgs 
               const size_t e = (size_t)m * g.N + n;
               if (g.addend) {
                 const uint2 av = *reinterpret_cast<const uint2 *>(g.addend + e);
-                o0 += gb_lo(av.x); o1 += gb_hi(av.x); o2 += gb_lo(av.y); o3 += gb_hi(av.y);
+                o0 += bf_lo(av.x); o1 += bf_hi(av.x); o2 += bf_lo(av.y); o3 += bf_hi(av.y);
               }
-              *reinterpret_cast<uint2 *>(g.y + e) = make_uint2(gb_pack2(o0, o1), gb_pack2(o2, o3));
+              *reinterpret_cast<uint2 *>(g.y + e) = make_uint2(pack2(o0, o1), pack2(o2, o3));
             }
           }
       }
@@ -1012,10 +995,10 @@ __global__ __launch_bounds__(64 * WGM * WGN, (BK == 32 && WGM * WGN == 8) ? 4 : 
     const char *base = lds + buf * STAGE;
 #pragma unroll
     for (int kk = 0; kk < KK; ++kk) {
-      const g_bf16x8 w0 = *reinterpret_cast<const g_bf16x8 *>(base + w_row + ch[kk]);
-      const g_bf16x8 w1 = *reinterpret_cast<const g_bf16x8 *>(base + w_row + 32 * ROWB + ch[kk]);
-      const g_bf16x8 x0 = *reinterpret_cast<const g_bf16x8 *>(base + x_row + ch[kk]);
-      const g_bf16x8 x1 = *reinterpret_cast<const g_bf16x8 *>(base + x_row + 32 * ROWB + ch[kk]);
+      const bf16x8 w0 = *reinterpret_cast<const bf16x8 *>(base + w_row + ch[kk]);
+      const bf16x8 w1 = *reinterpret_cast<const bf16x8 *>(base + w_row + 32 * ROWB + ch[kk]);
+      const bf16x8 x0 = *reinterpret_cast<const bf16x8 *>(base + x_row + ch[kk]);
+      const bf16x8 x1 = *reinterpret_cast<const bf16x8 *>(base + x_row + 32 * ROWB + ch[kk]);
       acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, x0, acc[0][0], 0, 0, 0);
       acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, x1, acc[0][1], 0, 0, 0);
       acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1, x0, acc[1][0], 0, 0, 0);
@@ -1090,11 +1073,11 @@ __global__ __launch_bounds__(64 * WGM * WGN, (BK == 32 && WGM * WGN == 8) ? 4 : 
         const size_t e = (size_t)m * g.N + n0 + wn * 64 + fr;
         if (g.addend) {
           const uint4 av = adv[i];
-          o[0] += gb_lo(av.x); o[1] += gb_hi(av.x); o[2] += gb_lo(av.y); o[3] += gb_hi(av.y);
-          o[4] += gb_lo(av.z); o[5] += gb_hi(av.z); o[6] += gb_lo(av.w); o[7] += gb_hi(av.w);
+          o[0] += bf_lo(av.x); o[1] += bf_hi(av.x); o[2] += bf_lo(av.y); o[3] += bf_hi(av.y);
+          o[4] += bf_lo(av.z); o[5] += bf_hi(av.z); o[6] += bf_lo(av.w); o[7] += bf_hi(av.w);
         }
-        *reinterpret_cast<uint4 *>(g.y + e) = make_uint4(gb_pack2(o[0], o[1]), gb_pack2(o[2], o[3]), gb_pack2(o[4], o[5]),
-                                                         gb_pack2(o[6], o[7]));
+        *reinterpret_cast<uint4 *>(g.y + e) = make_uint4(pack2(o[0], o[1]), pack2(o[2], o[3]), pack2(o[4], o[5]),
+                                                         pack2(o[6], o[7]));
       }
     }
     if (EP == 2 && pass == 0) __builtin_amdgcn_s_waitcnt(0xc07f);  // the rows are read before the second half overwrites them
@@ -1219,10 +1202,10 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN == 8) ? 4 : 1) void k_co
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
       const int ch = kk ? ch1 : ch0;
-      const g_bf16x8 w0 = *reinterpret_cast<const g_bf16x8 *>(bs + w_row + ch);
-      const g_bf16x8 w1 = *reinterpret_cast<const g_bf16x8 *>(bs + w_row + 32 * ROWB + ch);
-      const g_bf16x8 x0 = *reinterpret_cast<const g_bf16x8 *>(bs + x_row + ch);
-      const g_bf16x8 x1 = *reinterpret_cast<const g_bf16x8 *>(bs + x_row + 32 * ROWB + ch);
+      const bf16x8 w0 = *reinterpret_cast<const bf16x8 *>(bs + w_row + ch);
+      const bf16x8 w1 = *reinterpret_cast<const bf16x8 *>(bs + w_row + 32 * ROWB + ch);
+      const bf16x8 x0 = *reinterpret_cast<const bf16x8 *>(bs + x_row + ch);
+      const bf16x8 x1 = *reinterpret_cast<const bf16x8 *>(bs + x_row + 32 * ROWB + ch);
       acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, x0, acc[0][0], 0, 0, 0);
       acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, x1, acc[0][1], 0, 0, 0);
       acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1, x0, acc[1][0], 0, 0, 0);
@@ -1314,11 +1297,11 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN == 8) ? 4 : 1) void k_co
         const size_t e = (size_t)m * g.Kout + kcol;
         if (g.addend) {
           const uint4 av = adv[i];
-          o[0] += gb_lo(av.x); o[1] += gb_hi(av.x); o[2] += gb_lo(av.y); o[3] += gb_hi(av.y);
-          o[4] += gb_lo(av.z); o[5] += gb_hi(av.z); o[6] += gb_lo(av.w); o[7] += gb_hi(av.w);
+          o[0] += bf_lo(av.x); o[1] += bf_hi(av.x); o[2] += bf_lo(av.y); o[3] += bf_hi(av.y);
+          o[4] += bf_lo(av.z); o[5] += bf_hi(av.z); o[6] += bf_lo(av.w); o[7] += bf_hi(av.w);
         }
-        *reinterpret_cast<uint4 *>(g.y + e) = make_uint4(gb_pack2(o[0], o[1]), gb_pack2(o[2], o[3]), gb_pack2(o[4], o[5]),
-                                                         gb_pack2(o[6], o[7]));
+        *reinterpret_cast<uint4 *>(g.y + e) = make_uint4(pack2(o[0], o[1]), pack2(o[2], o[3]), pack2(o[4], o[5]),
+                                                         pack2(o[6], o[7]));
       }
     }
     if (EP == 2 && pass == 0) __builtin_amdgcn_s_waitcnt(0xc07f);
@@ -1335,9 +1318,6 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN == 8) ? 4 : 1) void k_co
 // token rows twice).  Tokens past M and feature blocks past Na / Nb read a 16-byte zero word instead.
 // The reduction is cut into `splits` ranges of whole stages (blockIdx.y); one range writes / adds into dW directly,
 // several write fp32 partials that k_tn_reduce folds in index order (deterministic, no atomics).
-typedef short g_s16x4 __attribute__((ext_vector_type(4)));
-typedef g_s16x4 __attribute__((address_space(3))) * lds_s16x4_ptr_t;
-
 struct TnArgs {
   const uint16_t *dy;  // [M][Na] bf16
   const uint16_t *x;   // [M][Nb] bf16
@@ -1567,7 +1547,7 @@ __global__ __launch_bounds__(256) void k_pack_bf16(const float *__restrict__ w, 
   for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += (int64_t)gridDim.x * 1024) {
     if (i + 3 < n) {
       const float4 v = *reinterpret_cast<const float4 *>(w + i);
-      *reinterpret_cast<uint2 *>(wp + i) = make_uint2(gb_pack2(v.x, v.y), gb_pack2(v.z, v.w));
+      *reinterpret_cast<uint2 *>(wp + i) = make_uint2(pack2(v.x, v.y), pack2(v.z, v.w));
     } else {
       for (int64_t j2 = i; j2 < n; ++j2) wp[j2] = __builtin_bit_cast(uint16_t, (__bf16)w[j2]);
     }
@@ -1581,10 +1561,11 @@ int launch_gemm_nt(const NtPlan &p, GbArgs g, hipStream_t st) {
   g.tiles_m = p.tiles_m;
   g.tiles_n = p.tiles_n;
   const dim3 grid(p.grid), block(64 * r.wgm * r.wgn);
-  if constexpr (r.family == NT_PLAIN) return launch_lds<k_gemm_bf16_nt<r.wgm, r.wgn, r.nst == 2>>(grid, block, r.lds(), st, g);
+  if constexpr (r.family == NT_PLAIN)
+    return salun_launch_lds<k_gemm_bf16_nt<r.wgm, r.wgn, r.nst == 2>>(grid, block, r.lds(), st, g);
   else if constexpr (r.family == NT_PERSISTENT)
-    return launch_lds<k_gemm_bf16_nt_p<r.wgm, r.wgn>>(grid, block, r.lds(), st, g, p.tiles_per_wg);
-  else return launch_lds<k_gemm_bf16_nt_r<r.wgm, r.wgn, r.nst, r.bk>>(grid, block, r.lds(), st, g);
+    return salun_launch_lds<k_gemm_bf16_nt_p<r.wgm, r.wgn>>(grid, block, r.lds(), st, g, p.tiles_per_wg);
+  else return salun_launch_lds<k_gemm_bf16_nt_r<r.wgm, r.wgn, r.nst, r.bk>>(grid, block, r.lds(), st, g);
 }
 
 template <int WGM, int WGN, int NST>
@@ -1592,14 +1573,14 @@ int launch_conv_ring(IrArgs g, hipStream_t st) {
   constexpr int BMt = 64 * WGM, BNt = 64 * WGN;
   g.tiles_m = (g.M + BMt - 1) / BMt;
   g.tiles_n = g.Kout / BNt;
-  return launch_lds<k_conv_bf16_ring<WGM, WGN, NST>>(dim3(g.tiles_m * g.tiles_n), dim3(64 * WGM * WGN),
-                                                     (size_t)NST * (BMt + BNt) * 64, st, g);
+  return salun_launch_lds<k_conv_bf16_ring<WGM, WGN, NST>>(dim3(g.tiles_m * g.tiles_n), dim3(64 * WGM * WGN),
+                                                           (size_t)NST * (BMt + BNt) * 64, st, g);
 }
 
 template <int WGA, int WGB, int RST, int NST>
 int launch_gemm_bf16_tn(const TnArgs &g, int splits, hipStream_t st) {
-  return launch_lds<k_gemm_bf16_tn<WGA, WGB, RST, NST>>(dim3(g.tiles_a * g.tiles_b * splits), dim3(64 * WGA * WGB),
-                                                        (size_t)NST * (64 * WGA + 64 * WGB) / 32 * RST * 64, st, g);
+  return salun_launch_lds<k_gemm_bf16_tn<WGA, WGB, RST, NST>>(dim3(g.tiles_a * g.tiles_b * splits), dim3(64 * WGA * WGB),
+                                                              (size_t)NST * (64 * WGA + 64 * WGB) / 32 * RST * 64, st, g);
 }
 
 }  // namespace

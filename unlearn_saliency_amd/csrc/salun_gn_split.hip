@@ -13,11 +13,9 @@
 // a = rstd * gamma[c], b = beta[c] - mu * a, o = x * a + b (the file is compiled without contraction), SiLU =
 // o * (1 / (1 + expf(-o))).  All loads and stores of x and y are 16 bytes.  S depends on cpg * HW and slab_vec4 only,
 // never on N or the device: the same inputs give the same bits and an image does not depend on the rest of its batch.
-#include "salun_common.h"
+#include "salun_device.h"
 
 namespace {
-
-__device__ __forceinline__ float gns_sigmoid(float y) { return 1.0f / (1.0f + expf(-y)); }
 
 // float4s per slab when the caller leaves the choice to us: 8 per lane.  The smallest GroupNorm of the VAE encoder at
 // 512 x 512 (512 channels in 32 groups at 64 x 64: 16384 float4s per group) then gives 32 * 8 = 256 workgroups for one
@@ -112,8 +110,8 @@ __global__ __launch_bounds__(256) void k_gns_apply(const float *x, float *y, con
     float4 o;
     o.x = t.x * a + b; o.y = t.y * a + b; o.z = t.z * a + b; o.w = t.w * a + b;
     if (SILU) {
-      o.x = o.x * gns_sigmoid(o.x); o.y = o.y * gns_sigmoid(o.y);
-      o.z = o.z * gns_sigmoid(o.z); o.w = o.w * gns_sigmoid(o.w);
+      o.x = o.x * salun_sigmoid(o.x); o.y = o.y * salun_sigmoid(o.y);
+      o.z = o.z * salun_sigmoid(o.z); o.w = o.w * salun_sigmoid(o.w);
     }
     yv[e] = o;
   }

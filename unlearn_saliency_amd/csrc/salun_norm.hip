@@ -10,7 +10,7 @@
 //                                                 dres = dz
 // Reductions: per (channel, slice-of-batch) workgroup partials in fp64, folded in a fixed order (deterministic).
 // Semantics follow torch.nn.BatchNorm2d (biased variance for normalisation, unbiased for running_var, momentum).
-#include "salun_common.h"
+#include "salun_device.h"
 
 namespace {
 
@@ -362,8 +362,6 @@ namespace {
 constexpr int GN_ITEMS = 16;            // most float4 per lane held in registers (ITEMS = 1, 2, 4, 8, 16; 0 = re-read mode)
 constexpr int GN_MAX_SEG = 1024;        // LDS slots for segment sums
 
-__device__ __forceinline__ float gn_sigmoid(float y) { return 1.0f / (1.0f + expf(-y)); }
-
 // sum over aligned groups of `r` lanes (r a power of two <= 64); every lane of the group gets the total
 __device__ __forceinline__ float seg_sum(float v, int r) {
   for (int off = 1; off < r; off <<= 1) v += __shfl_xor(v, off, 64);
@@ -433,8 +431,8 @@ __global__ __launch_bounds__(256) void k_gn_fwd(const float *__restrict__ x, flo
     float4 o;
     o.x = t.x * a + b; o.y = t.y * a + b; o.z = t.z * a + b; o.w = t.w * a + b;
     if (SILU) {
-      o.x = o.x * gn_sigmoid(o.x); o.y = o.y * gn_sigmoid(o.y);
-      o.z = o.z * gn_sigmoid(o.z); o.w = o.w * gn_sigmoid(o.w);
+      o.x = o.x * salun_sigmoid(o.x); o.y = o.y * salun_sigmoid(o.y);
+      o.z = o.z * salun_sigmoid(o.z); o.w = o.w * salun_sigmoid(o.w);
     }
     yv[e] = o;
   };
@@ -482,7 +480,7 @@ __global__ __launch_bounds__(256) void k_gn_bwd(const float *__restrict__ dz, co
     xh.x = (xt.x - mu) * rs; xh.y = (xt.y - mu) * rs; xh.z = (xt.z - mu) * rs; xh.w = (xt.w - mu) * rs;
     if (SILU) {
       const float y0 = xh.x * ga + be, y1 = xh.y * ga + be, y2 = xh.z * ga + be, y3 = xh.w * ga + be;
-      const float s0 = gn_sigmoid(y0), s1 = gn_sigmoid(y1), s2 = gn_sigmoid(y2), s3 = gn_sigmoid(y3);
+      const float s0 = salun_sigmoid(y0), s1 = salun_sigmoid(y1), s2 = salun_sigmoid(y2), s3 = salun_sigmoid(y3);
       gt.x = gt.x * (s0 * (1.0f + y0 * (1.0f - s0)));
       gt.y = gt.y * (s1 * (1.0f + y1 * (1.0f - s1)));
       gt.z = gt.z * (s2 * (1.0f + y2 * (1.0f - s2)));

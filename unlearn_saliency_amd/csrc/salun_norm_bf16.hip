@@ -11,29 +11,9 @@
 // channels (one 16-byte load per pixel) and strides over pixels, so loads are full rows and per-channel sums stay in
 // registers; group sums are formed afterwards from the per-channel partials (a group's channels are only 20..160 bytes
 // of a pixel's row — reading by group would waste most of every cache line).
-#include "salun_common.h"
+#include "salun_device.h"
 
 namespace {
-
-__device__ __forceinline__ uint16_t f2bf(float f) { return __builtin_bit_cast(uint16_t, (__bf16)f); }  // v_cvt_pk_bf16_f32: RNE
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-  bf16x2_t v;
-  v[0] = (__bf16)a; v[1] = (__bf16)b;
-  return __builtin_bit_cast(uint32_t, v);
-}
-__device__ __forceinline__ float bf2f(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
-__device__ __forceinline__ void unpack8(const uint4 v, float (&f)[8]) {
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { f[2 * j] = bf2f((uint16_t)(w[j] & 0xffffu)); f[2 * j + 1] = bf2f((uint16_t)(w[j] >> 16)); }
-}
-__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
-  uint32_t o[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) o[j] = pack2(f[2 * j], f[2 * j + 1]);
-  return make_uint4(o[0], o[1], o[2], o[3]);
-}
 
 // Workspace layout (floats): part[N][chunks][C][2] | mr[N][G][2] (mean, rstd) lives in its own output | ab[N][C][2]
 constexpr int GN_CHUNKS_MAX = 64;

@@ -15,7 +15,7 @@
 // The segment table lives in device memory (it is built once per model); both kernels re-derive the compact prefix
 // from it in LDS and VERIFY it against n and n_sel before touching memory: a table that is not ascending, leaves
 // [0, n) or does not sum to n_sel makes the round a no-op and raises the error flag that salun_prune_status reports.
-#include "salun_common.h"
+#include "salun_device.h"
 
 namespace {
 
@@ -27,8 +27,6 @@ struct PruneHdr {
   uint32_t bad_table;  // a kernel of the last round refused the segment table
   uint32_t pad[63];
 };
-
-inline size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
 
 struct WsLayout {
   size_t off_hdr, off_keys, off_sel, bytes;

@@ -10,30 +10,9 @@
 //
 // LayerNorm: one wave per token row (C = 320 / 640 / 1280 channels = 40 / 80 / 160 octets of 8 bf16); a lane owns the
 // octets lane, lane+64, lane+128 (<= 3), so the row stays in registers between the statistics and the normalise step.
-#include "salun_common.h"
+#include "salun_device.h"
 
 namespace {
-
-__device__ __forceinline__ float bf2f(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-  bf16x2_t v;
-  v[0] = (__bf16)a; v[1] = (__bf16)b;
-  return __builtin_bit_cast(uint32_t, v);
-}
-__device__ __forceinline__ void unpack8(const uint4 v, float (&f)[8]) {
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { f[2 * j] = bf2f((uint16_t)(w[j] & 0xffffu)); f[2 * j + 1] = bf2f((uint16_t)(w[j] >> 16)); }
-}
-__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
-  return make_uint4(pack2(f[0], f[1]), pack2(f[2], f[3]), pack2(f[4], f[5]), pack2(f[6], f[7]));
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 constexpr int LN_MAXO = 4;        // octets per lane: C <= 2048
 constexpr int LN_ROWS_PER_WG = 4; // one wave per row
@@ -57,7 +36,7 @@ __global__ __launch_bounds__(256) void k_ln16_fwd(const uint16_t *__restrict__ x
       for (int j = 0; j < 8; ++j) s += v[i][j];
     }
   }
-  const float mean = wave_sum(s) / (float)C;
+  const float mean = salun_wave_sum_all(s) / (float)C;
   float q = 0.f;
 #pragma unroll
   for (int i = 0; i < LN_MAXO; ++i)
@@ -65,7 +44,7 @@ __global__ __launch_bounds__(256) void k_ln16_fwd(const uint16_t *__restrict__ x
 #pragma unroll
       for (int j = 0; j < 8; ++j) { const float d = v[i][j] - mean; q += d * d; }
     }
-  const float rstd = rsqrtf(wave_sum(q) / (float)C + eps);
+  const float rstd = rsqrtf(salun_wave_sum_all(q) / (float)C + eps);
   if (lane == 0 && stats) stats[row] = make_float2(mean, rstd);
 #pragma unroll
   for (int i = 0; i < LN_MAXO; ++i) {
@@ -120,7 +99,7 @@ __global__ __launch_bounds__(256) void k_ln16_bwd(const uint16_t *__restrict__ d
         }
       }
     }
-    const float m1 = wave_sum(s1) / (float)C, m2 = wave_sum(s2) / (float)C;
+    const float m1 = salun_wave_sum_all(s1) / (float)C, m2 = salun_wave_sum_all(s2) / (float)C;
 #pragma unroll
     for (int i = 0; i < LN_MAXO; ++i) {
       const int o = lane + 64 * i;

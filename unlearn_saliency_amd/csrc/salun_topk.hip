@@ -41,7 +41,7 @@
 //   selection step itself, grid barriers between passes (monotonic counter, agent-scope release/acquire, bounded
 //   spin), per-chunk tie prefixes when a threshold splits a run of equal keys, one write pass.  When launched behind
 //   the fast route it returns at once unless `fail` (or the zero-tie flag) is set.
-#include "salun_common.h"
+#include "salun_device.h"
 #include <cmath>
 #include <cstdlib>
 
@@ -1679,7 +1679,6 @@ __global__ __launch_bounds__(SALUN_BLOCK) void k_sum_partials_i64(const u64 *__r
 // =====================================================================================================
 //                                              host side
 // =====================================================================================================
-inline size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
 inline int64_t chunks_of(int64_t n) { return (n + CHUNK - 1) / CHUNK; }
 
 inline int sample_size(int64_t n) {
@@ -1783,19 +1782,16 @@ inline WsLayout ws_layout(int64_t n, int nk) {
 }
 
 int g_cu_count = 0;
-unsigned long long g_fullscan_attr = 0;  // one bit per device: the dynamic-LDS opt-in is per device
+unsigned long long g_cu_count_done = 0;  // one bit per device
 inline int fullscan_grid(int64_t n) {
-  if (salun_once_needed(&g_fullscan_attr)) {
-    // 2 KiB + 16 x 4 KiB of dynamic LDS at the maximum threshold count: above the 64 KiB default
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_fullscan), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              96 * 1024);
+  if (salun_once_needed(&g_cu_count_done)) {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) == hipSuccess &&
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
       g_cu_count = cus;   // (devices of one node are the same part)
     else if (g_cu_count == 0)
       g_cu_count = 64;
-    salun_once_mark(&g_fullscan_attr);
+    salun_once_mark(&g_cu_count_done);
   }
   int64_t g = 2 * (int64_t)g_cu_count;  // resident with room to spare: the grid barrier needs every workgroup running
   if (g > 512) g = 512;
@@ -1870,11 +1866,10 @@ inline int run_fast_tail(const float *acc, int64_t n, const KList &kl, const Mas
     hipLaunchKernelGGL(k_finish<false>, dim3(nk * L.gf), dim3(1024), 0, st, P.fs, pub, P.list2, P.seg_cnt, L.gr, L.seg_cap,
                        P.wg_min, L.grid, P.fin, nk, mp);
   SALUN_LAUNCH_CHECK();
+  // 2 KiB + 4 KiB per threshold of dynamic LDS: above the default limit from 12 thresholds on
   const size_t lds_bytes = D0_BINS + sizeof(uint32_t) * (size_t)(nk < 2 ? 2 : nk) * 1024;
-  hipLaunchKernelGGL(k_fullscan, dim3(fullscan_grid(n)), dim3(SALUN_BLOCK), lds_bytes, st, acc, n, kl, mp, pub, full, P.fs,
-                     tie, 0, (int)aligned, (int)maligned, (int)values_only);
-  SALUN_LAUNCH_CHECK();
-  return SALUN_OK;
+  return salun_launch_lds<k_fullscan>(dim3(fullscan_grid(n)), dim3(SALUN_BLOCK), lds_bytes, st, acc, n, kl, mp, pub, full,
+                                      P.fs, tie, 0, (int)aligned, (int)maligned, (int)values_only);
 }
 
 }  // namespace
@@ -1931,6 +1926,7 @@ SALUN_EXPORT int salun_mask_topk_ex(const float *acc, int64_t n, const int64_t *
     void *args[] = {(void *)&acc, (void *)&n, (void *)&kl, (void *)&mp, (void *)&pub, (void *)&full, (void *)&no_fs,
                     (void *)&tie, (void *)&always, (void *)&al, (void *)&mal, (void *)&vo};
     const int grid = fullscan_grid(n);
+    if (salun_allow_lds<k_fullscan>(lds_bytes) != SALUN_OK) return SALUN_EIO;
     if (hipLaunchCooperativeKernel(reinterpret_cast<const void *>(k_fullscan), dim3(grid), dim3(SALUN_BLOCK), args,
                                    (unsigned)lds_bytes, st) != hipSuccess) {
       (void)hipGetLastError();

@@ -1085,6 +1085,27 @@ int salun_conv2d_infer(const float *x /*dev*/, const float *w /*dev*/, const flo
 int salun_conv2d_infer_route(int N, int C, int H, int W, int K, int R, int stride, int pad, int P, int Q, int tile,
                              char *buf, size_t buflen);
 
+/* K27 with a nearest-neighbour 2x input: the decoder's Upsample in one launch.
+ * Replaces  torch.nn.functional.interpolate(x, scale_factor=2.0, mode="nearest")  followed by  self.conv  (3 x 3,
+ * stride 1, padding 1) in  Upsample.forward  (ldm/modules/diffusionmodules/model.py:53-57).
+ *   y = act( conv(up2(x), w) * scale[k] + shift[k] + addend ),   up2(x)[n,c,i,j] = x[n,c,i>>1,j>>1]
+ * up2(x) is the VIRTUAL [N, C, 2H, 2W] map: it is never written.  H and W are the STORED sizes of x; P, Q, pad, the
+ * epilogue, the reduction order and the tiles are those of salun_conv2d_infer applied to the virtual map, so the bits
+ * equal those of salun_conv2d_infer on the materialised up2(x) with the same tile.  The halo test is made in virtual
+ * coordinates (0 <= ih < 2H) before the shift: a tap at virtual row -1 or 2H contributes zero.
+ * Domain: that of salun_conv2d_infer on (N, C, 2H, 2W, K, R, stride, pad, P, Q), narrowed to R == 3, stride == 1,
+ * C a multiple of 8, 1 <= H, W <= 512.  Both reduction orders and all three tiles are served.
+ * SALUN_EINVAL (nothing is written): as salun_conv2d_infer.
+ * salun_conv2d_infer_up2_route: the plain label with `^2` after the filter:
+ * infer<3,1>^2/<pixels>x<channels>/<fast|generic>/B<workgroups>. */
+int salun_conv2d_infer_up2(const float *x /*dev, N*C*H*W*/, const float *w /*dev*/,
+                           const float *scale /*dev, K, or NULL*/, const float *shift /*dev, K, or NULL*/,
+                           const float *addend /*dev, N*K*P*Q, or NULL*/, float *y /*dev, N*K*P*Q*/, int N, int C, int H,
+                           int W, int K, int R, int stride, int pad, int P, int Q, int relu, int tile,
+                           salun_stream_t stream);
+int salun_conv2d_infer_up2_route(int N, int C, int H, int W, int K, int R, int stride, int pad, int P, int Q, int tile,
+                                 char *buf, size_t buflen);
+
 /* MaxPool2d(kernel_size=3, stride=2, padding=1), forward only (csrc/salun_pool.hip, beside K24).
  * Replaces  resnet34().maxpool  (DDPM/classifier_evaluation.py:135).
  * x [NC, H, W] (contiguous), y [NC, (H+1)/2, (W+1)/2], any H, W >= 1.  Padding acts as -inf.  Selection is that of
@@ -1173,6 +1194,36 @@ int salun_gn_split_forward(const float *x /*dev*/, float *y /*dev*/, const float
 int salun_vae_posterior_sample(const float *moments /*dev, B*Cm*hw*/, int Cm, int zc, int64_t hw, int64_t B,
                                const int64_t *image_ids /*dev, B*/, uint64_t seed, int64_t draw, double scale,
                                int deterministic, float *z /*dev, B*zc*hw*/, salun_stream_t stream);
+
+/* The decoded image as bytes (csrc/salun_vae.hip).  Replaces  image = (image / 2 + 0.5).clamp(0, 1);
+ * image.permute(0, 2, 3, 1).numpy();  (image * 255).round().astype("uint8")  of SD/eval-scripts/generate-images.py.
+ * x [B, Cp, hw] fp32, out [B, hw, C] uint8, 1 <= C <= min(Cp, SALUN_DECODED_U8_MAX_C): the first C of Cp planes are read,
+ * so the channel-padded output of the decoder's conv_out is read in place.  Per element, every operation rounded by
+ * itself:  v = x * 0.5f;  v = v + 0.5f;  v = min(max(v, 0), 1);  v = v * 255.f;  u8 = rintf(v)  (half to even, as
+ * numpy's round).  A NaN gives 0.  Any hw; 64-bit indexing.  salun_images_to_u8 is another rule and stays.
+ * SALUN_EINVAL (nothing is written): B or hw < 1, C outside its range, B Cp hw > 2^40, a NULL pointer, x == out, x off
+ * 4-byte alignment. */
+#define SALUN_DECODED_U8_MAX_C 4
+int salun_decoded_to_u8(const float *x /*dev, B*Cp*hw*/, int Cp, int C, int64_t hw, int64_t B,
+                        uint8_t *out /*dev, B*hw*C*/, salun_stream_t stream);
+
+/* One step of the linear multistep (LMS) sampler of the evaluation script on B latents of chw floats, one launch
+ * (csrc/salun_sampler.hip; SD/lms.py computes the coefficients on the host in float64).
+ *   guided != 0: eps2 is ONE batched U-Net pass, rows [0, B) unconditional (e_u), rows [B, 2B) conditional (e_c), read
+ *                in place;  d = e_u + scale * (e_c - e_u)
+ *   guided == 0: eps2 holds B rows, d = eps2, and scale must be 1 (else SALUN_EINVAL)
+ *   hist[slot] = d                                  (hist: a ring of SALUN_LMS_ORDER rows of B * chw floats)
+ *   a = x + c[0] * d;  a = a + c[j] * hist[(slot - j) mod SALUN_LMS_ORDER]  for j = 1 .. order - 1, in that order
+ *   x_new = a;   x_in[r] = a / den  for r = 0 (and r = 1 when guided): the [2B, chw] or [B, chw] input of the next pass
+ * Every operation is one correctly rounded fp32 operation (no contraction, IEEE division); c[] and den are rounded to
+ * fp32 first; den = sqrt(sigma_next^2 + 1) is the host's value.  x_new may be x; x_in may be NULL.
+ * SALUN_EINVAL (nothing is written): order outside [1, SALUN_LMS_ORDER], slot outside [0, SALUN_LMS_ORDER), B or chw
+ * < 0, den == 0, a NULL x, eps2, hist or x_new, hist or x_in equal to another argument. */
+#define SALUN_LMS_ORDER 4
+int salun_lms_step(const float *x /*dev*/, const float *eps2 /*dev, 2B or B rows*/, int guided, double scale,
+                   float *hist /*dev, SALUN_LMS_ORDER*B*chw*/, int slot, int order, double c0, double c1, double c2,
+                   double c3, double den, float *x_new /*dev*/, float *x_in /*dev, 2B or B rows, or NULL*/, int64_t B,
+                   int64_t chw, salun_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -308,3 +308,170 @@ class EncoderPlan:
             self._counter += B
             return self.encode(x, ids, seed, 0, False, 1.0)
         return encode
+
+
+# ------------------------------------------------------------------------------------------------------ the decoder
+# The other half of the first stage (the reference's `Decoder`, ldm/modules/diffusionmodules/model.py:496-625, behind
+# `post_quant_conv`, as AutoencoderKL.decode chains them): what SD/eval-scripts/generate-images.py turns latents into
+# images with.  `DecoderKLLite` is the module tree under the reference's names (`decoder.*`, `post_quant_conv.*`); its
+# `forward` runs library ops and is the yardstick.  `DecoderPlan(model)` is the path a user runs, fp32 and forward only:
+#   * Conv2d, GroupNorm(+SiLU), ResnetBlock and mid.attn_1 exactly as EncoderPlan runs them (K27 / K28 / K15);
+#   * Upsample (F.interpolate(scale_factor=2, mode="nearest") + conv 3 x 3) is ONE launch of K27's up2 form
+#     (conv_infer.conv_up2_bn_act): the gather reads x[ih >> 1][iw >> 1]; the four-fold tensor is never written;
+#   * zero-padding, once, when the plan is made:
+#         post_quant_conv  C = 4 -> 8, K = 4 -> 32  (the scaled latent is written into a zeroed 8-channel buffer)
+#         conv_in          C = 4 -> 32              (it reads post_quant_conv's padded output in place)
+#         conv_out         K = 3 -> 32              (decode_u8 reads the first three planes in place)
+IGNORED_PREFIXES_DECODER = ("encoder.", "quant_conv.", "loss.", "model_ema.")
+
+
+class Upsample(nn.Module):
+    def __init__(self, c: int):
+        super().__init__()
+        self.conv = nn.Conv2d(c, c, 3, 1, 1)
+
+    def forward(self, x):
+        return self.conv(F.interpolate(x, scale_factor=2.0, mode="nearest"))
+
+
+class Decoder(nn.Module):
+    def __init__(self, *, ch, out_ch, ch_mult=(1, 2, 4, 8), num_res_blocks, attn_resolutions=(), in_channels=3,
+                 resolution, z_channels, **ignored):
+        super().__init__()
+        self.ch, self.in_channels, self.resolution = ch, in_channels, resolution
+        self.num_resolutions, self.num_res_blocks = len(ch_mult), num_res_blocks
+        cin = ch * ch_mult[-1]
+        res = resolution // 2 ** (self.num_resolutions - 1)
+        self.conv_in = nn.Conv2d(z_channels, cin, 3, 1, 1)
+        self.mid = _Bag()
+        self.mid.block_1, self.mid.attn_1, self.mid.block_2 = ResnetBlock(cin, cin), AttnBlock(cin), ResnetBlock(cin, cin)
+        levels = []
+        for i in reversed(range(self.num_resolutions)):
+            lvl = _Bag()
+            lvl.block, lvl.attn = nn.ModuleList(), nn.ModuleList()
+            for _ in range(num_res_blocks + 1):
+                lvl.block.append(ResnetBlock(cin, ch * ch_mult[i]))
+                cin = ch * ch_mult[i]
+                if res in attn_resolutions:
+                    lvl.attn.append(AttnBlock(cin))
+            if i != 0:
+                lvl.upsample = Upsample(cin)
+                res *= 2
+            levels.insert(0, lvl)                    # up[0] is the finest level, as in the reference
+        self.up = nn.ModuleList(levels)
+        self.norm_out = _norm(cin)
+        self.conv_out = nn.Conv2d(cin, out_ch, 3, 1, 1)
+
+    def forward(self, z):
+        h = self.conv_in(z)
+        h = self.mid.block_2(self.mid.attn_1(self.mid.block_1(h)))
+        for i in reversed(range(self.num_resolutions)):
+            lvl = self.up[i]
+            for j, blk in enumerate(lvl.block):
+                h = blk(h)
+                if len(lvl.attn):
+                    h = lvl.attn[j](h)
+            if i != 0:
+                h = lvl.upsample(h)
+        return self.conv_out(_swish(self.norm_out(h)))
+
+
+class DecoderKLLite(nn.Module):
+    """`post_quant_conv` + `decoder` of AutoencoderKL.  `forward(z)` = the image [B, out_ch, f h, f w] of an UNSCALED
+    latent on library ops."""
+
+    def __init__(self, ddconfig: Optional[dict] = None, embed_dim: int = V1_EMBED_DIM):
+        super().__init__()
+        self.ddconfig = dict(ddconfig or V1_DDCONFIG)
+        self.embed_dim = int(embed_dim)
+        self.decoder = Decoder(**self.ddconfig)
+        self.post_quant_conv = nn.Conv2d(self.embed_dim, self.ddconfig["z_channels"], 1)
+        self.requires_grad_(False).eval()
+
+    def forward(self, z):
+        return self.decoder(self.post_quant_conv(z))
+
+    def load_compvis(self, source) -> "DecoderKLLite":
+        """`source`: a path or a dict; an SD-v1 CompVis checkpoint (["state_dict"], keys under `first_stage_model.`) or
+        a bare autoencoder state dict.  Encoder, quant_conv, loss and EMA keys are ignored; a missing or mis-shaped
+        decoder key is an error that names it."""
+        sd = torch.load(source, map_location="cpu", weights_only=False) if isinstance(source, (str, bytes)) or \
+            hasattr(source, "__fspath__") else source
+        sd = sd.get("state_dict", sd)
+        pre = "first_stage_model."
+        if any(k.startswith(pre) for k in sd):
+            sd = {k[len(pre):]: v for k, v in sd.items() if k.startswith(pre)}
+        sd = {k: v for k, v in sd.items() if not k.startswith(IGNORED_PREFIXES_DECODER)}
+        own = self.state_dict()
+        for k, t in own.items():
+            if k not in sd:
+                raise KeyError(f"load_compvis: the checkpoint has no `{k}`")
+            if tuple(sd[k].shape) != tuple(t.shape):
+                raise ValueError(f"load_compvis: `{k}` has shape {tuple(sd[k].shape)}, the decoder needs {tuple(t.shape)}")
+        extra = sorted(set(sd) - set(own))
+        if extra:
+            raise KeyError(f"load_compvis: unexpected key `{extra[0]}`" + (f" (and {len(extra) - 1} more)" if len(extra) > 1 else ""))
+        self.load_state_dict({k: sd[k] for k in own})
+        return self
+
+
+class DecoderPlan:
+    """The decoder of `model` (a DecoderKLLite on a ROCm device, fp32) on K27 (plain and up2) / K28 / K15 and the
+    byte kernel.  Owns zero-padded copies of the three weights K27 needs padded, made once here: re-plan after loading
+    other weights into the model."""
+
+    _pad = staticmethod(EncoderPlan._pad)
+    _conv = EncoderPlan._conv
+    _gn = staticmethod(EncoderPlan._gn)
+    _res = EncoderPlan._res
+    _attn = EncoderPlan._attn
+    _product = staticmethod(EncoderPlan._product)
+
+    def __init__(self, model: DecoderKLLite):
+        p = next(model.parameters())
+        if not p.is_cuda or p.dtype != torch.float32:
+            raise RuntimeError("DecoderPlan: the model must be fp32 on a ROCm device (no CPU path)")
+        self.model, self.device = model, p.device
+        dec, pq = model.decoder, model.post_quant_conv
+        self.zc, self.zc_pad = model.embed_dim, _ceil_to(model.embed_dim, 8)
+        self.out_ch = dec.conv_out.out_channels
+        self.factor = 2 ** (dec.num_resolutions - 1)
+        kq = _ceil_to(pq.out_channels, 32)
+        self._padded = {id(pq): self._pad(pq, self.zc_pad, kq),
+                        id(dec.conv_in): self._pad(dec.conv_in, kq, dec.conv_in.out_channels),
+                        id(dec.conv_out): self._pad(dec.conv_out, dec.conv_out.in_channels, _ceil_to(self.out_ch, 32))}
+
+    def _up(self, up: Upsample, x):
+        from .. import conv_infer
+        return conv_infer.conv_up2_bn_act(x, up.conv.weight, None, up.conv.bias)
+
+    @torch.no_grad()
+    def decode_padded(self, z: torch.Tensor, scale: float = SCALE_FACTOR) -> torch.Tensor:
+        """z [B, embed_dim, h, w] -> [B, Kp, f h, f w], Kp = out_ch rounded up to K27's multiple of 32; channels past
+        out_ch are zero."""
+        m, dec = self.model, self.model.decoder
+        if z.dim() != 4 or z.shape[1] != self.zc:
+            raise ValueError(f"DecoderPlan: a latent of shape {tuple(z.shape)}, the decoder takes [B, {self.zc}, h, w]")
+        B, _, hh, ww = z.shape
+        buf = torch.zeros((B, self.zc_pad, hh, ww), dtype=torch.float32, device=self.device)
+        torch.mul(z.to(self.device, torch.float32), 1.0 / scale, out=buf[:, :self.zc])     # 1 / scale * z: one rounding
+        h = self._conv(dec.conv_in, self._conv(m.post_quant_conv, buf))
+        h = self._res(dec.mid.block_2, self._attn(dec.mid.attn_1, self._res(dec.mid.block_1, h)))
+        for i in reversed(range(dec.num_resolutions)):
+            lvl = dec.up[i]
+            for j, blk in enumerate(lvl.block):
+                h = self._res(blk, h)
+                if len(lvl.attn):
+                    h = self._attn(lvl.attn[j], h)
+            if i != 0:
+                h = self._up(lvl.upsample, h)
+        return self._conv(dec.conv_out, self._gn(dec.norm_out, h, True))
+
+    def decode(self, z: torch.Tensor, scale: float = SCALE_FACTOR) -> torch.Tensor:
+        """z = scale * (a latent of the first stage) -> the image, fp32 [B, out_ch, f h, f w] in about [-1, 1]."""
+        return self.decode_padded(z, scale)[:, :self.out_ch].contiguous()
+
+    def decode_u8(self, z: torch.Tensor, scale: float = SCALE_FACTOR) -> torch.Tensor:
+        """-> uint8 [B, f h, f w, out_ch] = round(clamp(image / 2 + 0.5, 0, 1) * 255), read from the padded output in place."""
+        from .. import ops_infer
+        return ops_infer.decoded_to_u8(self.decode_padded(z, scale), self.out_ch)

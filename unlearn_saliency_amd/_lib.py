@@ -73,6 +73,8 @@ SALUN_RESAMPLE_MAX_LDS = 65536
 SALUN_INFER_TILE_AUTO, SALUN_INFER_TILE_64X64, SALUN_INFER_TILE_128X64, SALUN_INFER_TILE_128X128 = 0, 1, 2, 3
 SALUN_U8_NORM_MAX_C = 4
 SALUN_GN_SPLIT_FLUSH = 16
+SALUN_DECODED_U8_MAX_C = 4
+SALUN_LMS_ORDER = 4
 
 # name -> (restype, argtypes); mirrors include/salun.h one to one
 # (tests/test_cabi.py checks this table against the header and the .so).
@@ -255,6 +257,11 @@ SIGNATURES = {
                                                          c_size_t, c_void_p]),
     "salun_vae_posterior_sample": (c_int, [c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_uint64, c_int64,
                                            c_double, c_int, c_void_p, c_void_p]),
+    "salun_conv2d_infer_up2": (c_int, [c_void_p] * 6 + [c_int] * 12 + [c_void_p]),
+    "salun_conv2d_infer_up2_route": (c_int, [c_int] * 11 + [ctypes.c_char_p, c_size_t]),
+    "salun_decoded_to_u8": (c_int, [c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p]),
+    "salun_lms_step": (c_int, [c_void_p, c_void_p, c_int, c_double, c_void_p, c_int, c_int] + [c_double] * 5 +
+                       [c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
 }
 
 _lib = None

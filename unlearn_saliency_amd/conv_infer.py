@@ -18,7 +18,7 @@ from . import _lib, ops_infer
 
 # calls that went to the library instead of K27 / the pool / the normalise kernel, by reason
 LIBRARY_INFER_CALLS = {"conv_shape": 0, "conv_dtype_or_autocast": 0, "conv_requires_grad": 0, "pool_dtype_or_autocast": 0,
-                       "norm_shape": 0}
+                       "norm_shape": 0, "conv_up2": 0}
 
 
 def library_infer_calls() -> int:
@@ -90,3 +90,25 @@ def u8_to_chw_norm(src: torch.Tensor, table: torch.Tensor, out: Optional[torch.T
         idx = src.long().permute(0, 3, 1, 2)
         return torch.stack([table.to(src.device)[c][idx[:, c]] for c in range(idx.shape[1])], 1)
     return ops_infer.u8_to_chw_norm(src.contiguous(), table, out)
+
+
+def conv_up2_bn_act(x: torch.Tensor, w: torch.Tensor, scale: Optional[torch.Tensor] = None,
+                    shift: Optional[torch.Tensor] = None, addend: Optional[torch.Tensor] = None, relu: bool = False,
+                    out: Optional[torch.Tensor] = None, tile: int = _lib.SALUN_INFER_TILE_AUTO) -> torch.Tensor:
+    """act(conv2d(interpolate(x, scale_factor=2, mode="nearest"), w, padding=1) * scale[k] + shift[k] + addend), forward
+    only: one K27 launch that gathers x[ih >> 1][iw >> 1]; the up-sampled tensor is never written."""
+    def library(reason):
+        LIBRARY_INFER_CALLS[reason] += 1
+        return _library_conv(F.interpolate(x, scale_factor=2.0, mode="nearest"), w, scale, shift, addend, relu, 1, 1)
+    ts = [t for t in (x, w, scale, shift, addend) if t is not None]
+    if not all(t.is_cuda and t.dtype == torch.float32 for t in ts) or torch.is_autocast_enabled() or \
+            (torch.is_grad_enabled() and any(t.requires_grad for t in ts)):
+        return library("conv_up2")
+    ok = x.dim() == 4 and w.dim() == 4 and w.shape[2] == w.shape[3] and w.shape[1] == x.shape[1] and x.shape[0] >= 1
+    if ok:
+        N, C, H, W = (int(v) for v in x.shape)
+        ok = ops_infer.conv2d_infer_up2_route(N, C, H, W, int(w.shape[0]), int(w.shape[2]), 1, 1, tile=tile) is not None
+    if not ok:
+        return library("conv_up2")
+    return ops_infer.conv2d_infer_up2(x.contiguous(), w.contiguous(), scale, shift,
+                                      None if addend is None else addend.contiguous(), relu, out, tile)

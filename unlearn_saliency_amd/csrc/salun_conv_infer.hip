@@ -36,6 +36,11 @@
 //   o = acc;  o = o * scale[k];  o = o + shift[k];  o = o + addend;  o = o < 0 ? 0 : o.
 // No atomics, no workspace: an element's bits depend on its own reduction only, not on the tile, the batch or the run.
 // Indexing is 64-bit wherever a tensor offset is formed.
+//
+// salun_conv2d_infer_up2 is the same kernel with UP2 = true: the input is gathered through the virtual nearest-neighbour
+// 2x map (x[ih >> 1][iw >> 1]), which the first-stage decoder's Upsample would otherwise write out at four times the
+// size of x and read back once.  The instantiations with UP2 = false compile as they did without it
+// (profiles/conv_infer_up2_resource_usage_{parent,head}.txt).
 #include "salun_device.h"
 #include <stdio.h>
 #include <string.h>
@@ -53,7 +58,11 @@ struct InferArgs {
   int nkt;        // channel tiles
 };
 
-template <int PB, int KB, bool GENERIC>
+// UP2: x is read through the virtual nearest-neighbour map up2(x)[n,c,i,j] = x[n,c,i>>1,j>>1] of 2H x 2W (g.H, g.W stay
+// the STORED sizes).  The halo test is made in virtual coordinates and the shift comes after it: virtual row -1 or 2H
+// is padding, not stored row 0 or H - 1.  Nothing else differs, so the bits are those of the plain kernel on the
+// materialised map.
+template <int PB, int KB, bool GENERIC, bool UP2>
 __global__ __launch_bounds__(256) void conv_infer(const InferArgs g) {
   constexpr int PT = PB / 64, KT = KB / 64;  // 32 x 32 accumulator tiles of a wave
   constexpr int AROW = KB + 4;
@@ -73,6 +82,7 @@ __global__ __launch_bounds__(256) void conv_infer(const InferArgs g) {
   const size_t HW = static_cast<size_t>(g.H) * g.W;
   const long long PQ = static_cast<long long>(g.P) * g.Q;
   const int J = g.C * RS;  // products per output element
+  const int VH = UP2 ? 2 * g.H : g.H, VW = UP2 ? 2 * g.W : g.W;  // the map the taps walk
 
   // ---- the pixel this thread stages: decomposed once
   const int bpix = tid % PB, brow0 = tid / PB;
@@ -121,9 +131,10 @@ __global__ __launch_bounds__(256) void conv_infer(const InferArgs g) {
       const int tap = st / cchunks, c0 = (st - tap * cchunks) * CC;
       const int r = tap / g.R, s = tap - r * g.R;
       const int ih = ih0 + r, iw = iw0 + s;
-      const bool ok = pvalid && ih >= 0 && ih < g.H && iw >= 0 && iw < g.W;  // the one halo test of (pixel, tap)
+      const bool ok = pvalid && ih >= 0 && ih < VH && iw >= 0 && iw < VW;  // the one halo test of (pixel, tap)
       bmask = ok ? ~0u : 0u;
-      const float *src = xr + static_cast<size_t>(c0 + brow0) * HW + (ok ? static_cast<size_t>(ih) * g.W + iw : 0);
+      const int sh = UP2 ? ih >> 1 : ih, sw = UP2 ? iw >> 1 : iw;
+      const float *src = xr + static_cast<size_t>(c0 + brow0) * HW + (ok ? static_cast<size_t>(sh) * g.W + sw : 0);
 #pragma unroll
       for (int i = 0; i < BN; ++i) breg[i] = src[static_cast<size_t>(i * BSTEP) * HW];
       const int wstep = c0 * RS + tap;
@@ -139,9 +150,10 @@ __global__ __launch_bounds__(256) void conv_infer(const InferArgs g) {
         const int c = jc / RS, tap = jc - c * RS;
         const int r = tap / g.R, s = tap - r * g.R;
         const int ih = ih0 + r, iw = iw0 + s;
-        const bool ok = pvalid && j < J && ih >= 0 && ih < g.H && iw >= 0 && iw < g.W;
+        const bool ok = pvalid && j < J && ih >= 0 && ih < VH && iw >= 0 && iw < VW;
         bmask |= ok ? (1u << i) : 0u;
-        breg[i] = xr[ok ? static_cast<size_t>(c) * HW + static_cast<size_t>(ih) * g.W + iw : 0];
+        const int sh = UP2 ? ih >> 1 : ih, sw = UP2 ? iw >> 1 : iw;
+        breg[i] = xr[ok ? static_cast<size_t>(c) * HW + static_cast<size_t>(sh) * g.W + sw : 0];
       }
 #pragma unroll
       for (int i = 0; i < AN; ++i) {
@@ -254,10 +266,17 @@ constexpr int TILE_PB[4] = {0, 64, 128, 128};
 constexpr int TILE_KB[4] = {0, 64, 64, 128};
 constexpr long long FILL = 256;  // one workgroup per CU
 
-// The ONE place that says whether a shape is served and by which instantiation: salun_conv2d_infer launches from it and
-// salun_conv2d_infer_route prints it.
-InferPlan plan_infer(int N, int C, int H, int W, int K, int R, int stride, int pad, int P, int Q, int tile) {
+// The ONE place that says whether a shape is served and by which instantiation: salun_conv2d_infer[_up2] launch from it
+// and salun_conv2d_infer[_up2]_route print it.  up2: H and W are the STORED sizes; the domain is the plain one applied
+// to the virtual 2H x 2W map, narrowed to what the decoder's Upsample needs (3 x 3, stride 1, C % 8 == 0, H, W <= 512).
+InferPlan plan_infer(int N, int C, int H, int W, int K, int R, int stride, int pad, int P, int Q, int tile,
+                     bool up2 = false) {
   InferPlan pl{};
+  if (up2) {
+    if (R != 3 || stride != 1 || C < 8 || C % 8 != 0 || H < 1 || H > 512 || W < 1 || W > 512) return pl;
+    H *= 2;
+    W *= 2;
+  }
   if (N < 1 || C < 1 || C > 65536 || K < 32 || K % 32 != 0 || K > 65536) return pl;
   if (R != 1 && R != 3 && R != 7) return pl;
   if (R != 7 && C % 8 != 0) return pl;
@@ -289,10 +308,41 @@ InferPlan plan_infer(int N, int C, int H, int W, int K, int R, int stride, int p
   return pl;
 }
 
-template <int PB, int KB>
+template <int PB, int KB, bool UP2>
 void launch(const InferPlan &pl, const InferArgs &a, hipStream_t st) {
-  if (pl.generic) hipLaunchKernelGGL((conv_infer<PB, KB, true>), dim3(static_cast<unsigned>(pl.blocks)), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((conv_infer<PB, KB, false>), dim3(static_cast<unsigned>(pl.blocks)), dim3(256), 0, st, a);
+  if (pl.generic) hipLaunchKernelGGL((conv_infer<PB, KB, true, UP2>), dim3(static_cast<unsigned>(pl.blocks)), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((conv_infer<PB, KB, false, UP2>), dim3(static_cast<unsigned>(pl.blocks)), dim3(256), 0, st, a);
+}
+
+template <bool UP2>
+int run_infer(const float *x, const float *w, const float *scale, const float *shift, const float *addend, float *y, int N,
+              int C, int H, int W, int K, int R, int stride, int pad, int P, int Q, int relu, int tile,
+              salun_stream_t stream) {
+  const InferPlan pl = plan_infer(N, C, H, W, K, R, stride, pad, P, Q, tile, UP2);
+  if (!pl.ok || !x || !w || !y || addend == y || x == y) return SALUN_EINVAL;
+  if (!salun_aligned4(x) || !salun_aligned4(w) || !salun_aligned4(y) || !salun_aligned4(scale) || !salun_aligned4(shift) ||
+      !salun_aligned4(addend))
+    return SALUN_EINVAL;
+  InferArgs a{x, w, scale, shift, addend, y, N, C, H, W, K, R, stride, pad, P, Q, relu ? 1 : 0, pl.npq, pl.nkt};
+  hipStream_t st = salun_hip_stream(stream);
+  if (pl.pb == 64) launch<64, 64, UP2>(pl, a, st);
+  else if (pl.kb == 64) launch<128, 64, UP2>(pl, a, st);
+  else launch<128, 128, UP2>(pl, a, st);
+  SALUN_LAUNCH_CHECK();
+  return SALUN_OK;
+}
+
+int route_infer(int N, int C, int H, int W, int K, int R, int stride, int pad, int P, int Q, int tile, bool up2, char *buf,
+                size_t buflen) {
+  const InferPlan pl = plan_infer(N, C, H, W, K, R, stride, pad, P, Q, tile, up2);
+  if (!pl.ok) return SALUN_EINVAL;
+  if (!buf) return SALUN_EINVAL;
+  char tmp[96];
+  snprintf(tmp, sizeof tmp, "infer<%d,%d>%s/%dx%d/%s/B%lld", R, stride, up2 ? "^2" : "", pl.pb, pl.kb,
+           pl.generic ? "generic" : "fast", pl.blocks);
+  if (strlen(tmp) + 1 > buflen) return SALUN_ENOSPC;
+  memcpy(buf, tmp, strlen(tmp) + 1);
+  return SALUN_OK;
 }
 
 }  // namespace
@@ -300,28 +350,21 @@ void launch(const InferPlan &pl, const InferArgs &a, hipStream_t st) {
 SALUN_EXPORT int salun_conv2d_infer(const float *x, const float *w, const float *scale, const float *shift,
                                     const float *addend, float *y, int N, int C, int H, int W, int K, int R, int stride,
                                     int pad, int P, int Q, int relu, int tile, salun_stream_t stream) {
-  const InferPlan pl = plan_infer(N, C, H, W, K, R, stride, pad, P, Q, tile);
-  if (!pl.ok || !x || !w || !y || addend == y || x == y) return SALUN_EINVAL;
-  if (!salun_aligned4(x) || !salun_aligned4(w) || !salun_aligned4(y) || !salun_aligned4(scale) || !salun_aligned4(shift) ||
-      !salun_aligned4(addend))
-    return SALUN_EINVAL;
-  InferArgs a{x, w, scale, shift, addend, y, N, C, H, W, K, R, stride, pad, P, Q, relu ? 1 : 0, pl.npq, pl.nkt};
-  hipStream_t st = salun_hip_stream(stream);
-  if (pl.pb == 64) launch<64, 64>(pl, a, st);
-  else if (pl.kb == 64) launch<128, 64>(pl, a, st);
-  else launch<128, 128>(pl, a, st);
-  SALUN_LAUNCH_CHECK();
-  return SALUN_OK;
+  return run_infer<false>(x, w, scale, shift, addend, y, N, C, H, W, K, R, stride, pad, P, Q, relu, tile, stream);
 }
 
 SALUN_EXPORT int salun_conv2d_infer_route(int N, int C, int H, int W, int K, int R, int stride, int pad, int P, int Q,
                                           int tile, char *buf, size_t buflen) {
-  const InferPlan pl = plan_infer(N, C, H, W, K, R, stride, pad, P, Q, tile);
-  if (!pl.ok) return SALUN_EINVAL;
-  if (!buf) return SALUN_EINVAL;
-  char tmp[96];
-  snprintf(tmp, sizeof tmp, "infer<%d,%d>/%dx%d/%s/B%lld", R, stride, pl.pb, pl.kb, pl.generic ? "generic" : "fast", pl.blocks);
-  if (strlen(tmp) + 1 > buflen) return SALUN_ENOSPC;
-  memcpy(buf, tmp, strlen(tmp) + 1);
-  return SALUN_OK;
+  return route_infer(N, C, H, W, K, R, stride, pad, P, Q, tile, false, buf, buflen);
+}
+
+SALUN_EXPORT int salun_conv2d_infer_up2(const float *x, const float *w, const float *scale, const float *shift,
+                                        const float *addend, float *y, int N, int C, int H, int W, int K, int R,
+                                        int stride, int pad, int P, int Q, int relu, int tile, salun_stream_t stream) {
+  return run_infer<true>(x, w, scale, shift, addend, y, N, C, H, W, K, R, stride, pad, P, Q, relu, tile, stream);
+}
+
+SALUN_EXPORT int salun_conv2d_infer_up2_route(int N, int C, int H, int W, int K, int R, int stride, int pad, int P, int Q,
+                                              int tile, char *buf, size_t buflen) {
+  return route_infer(N, C, H, W, K, R, stride, pad, P, Q, tile, true, buf, buflen);
 }

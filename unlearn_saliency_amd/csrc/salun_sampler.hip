@@ -22,6 +22,12 @@
 //                         torch (cat, chunk, four torch.full, ten elementwise operations) between two U-Net passes, 50
 //                         times per ESD iteration.
 //
+//     salun_lms_step      one step of the evaluation script's linear multistep sampler (SD/lms.py): the
+//                         guided derivative from the two halves of ONE batched U-Net output, stored into a 4-deep ring,
+//                         x + c0 d + c1 d1 + ... accumulated in that order, the new x written, and x_new / den written
+//                         into both halves of the tensor the next pass reads.  The coefficients are the host's (closed
+//                         form in float64); same rounding rules as salun_ldm_ddim_step.
+//
 // All of them are memory / latency bound; 16-byte loads and stores where the shapes allow.
 #include "salun_common.h"
 
@@ -344,6 +350,40 @@ int step_grid(int64_t items) {
   return (int)b;
 }
 
+struct LmsCoef {
+  float scale, c[4], den;
+};
+
+// One element per thread, grid-stride.  x_new may alias x (an element is read before it is written, by one thread);
+// hist and x_in alias nothing (the entry point refuses it).  eu == nullptr: no guidance.
+__global__ __launch_bounds__(SALUN_BLOCK) void k_lms_step(const float *x, const float *eu, const float *ec, LmsCoef k,
+                                                          float *hist, int slot, int order, float *xn, float *xin,
+                                                          int64_t total) {
+  for (int64_t i = (int64_t)blockIdx.x * SALUN_BLOCK + threadIdx.x; i < total; i += (int64_t)gridDim.x * SALUN_BLOCK) {
+    float d = ec[i];
+    if (eu) {
+      const float u = eu[i];
+      const float df = d - u;
+      const float sd = k.scale * df;
+      d = u + sd;
+    }
+    hist[(int64_t)slot * total + i] = d;
+    const float t0 = k.c[0] * d;
+    float a = x[i] + t0;
+    for (int j = 1; j < order; ++j) {
+      const float dj = hist[(int64_t)((slot - j) & 3) * total + i];
+      const float t = k.c[j] * dj;
+      a = a + t;
+    }
+    xn[i] = a;
+    if (xin) {
+      const float v = a / k.den;
+      xin[i] = v;
+      if (eu) xin[total + i] = v;
+    }
+  }
+}
+
 }  // namespace
 
 // ================================================================== C-ABI =======
@@ -404,6 +444,28 @@ SALUN_EXPORT int salun_ldm_ddim_step(const float *x, const float *eps2, int guid
     hipLaunchKernelGGL(k_ldm_ddim_step<1>, dim3(step_grid(n)), dim3(SALUN_BLOCK), 0, st, x, eu, ec, k, z, x_prev, x0_out,
                        n);
   }
+  SALUN_LAUNCH_CHECK();
+  return SALUN_OK;
+}
+
+SALUN_EXPORT int salun_lms_step(const float *x, const float *eps2, int guided, double scale, float *hist, int slot,
+                                int order, double c0, double c1, double c2, double c3, double den, float *x_new,
+                                float *x_in, int64_t B, int64_t chw, salun_stream_t stream) {
+  static_assert(SALUN_LMS_ORDER == 4, "the ring index is masked with 3");
+  if (B < 0 || chw < 0 || order < 1 || order > SALUN_LMS_ORDER || slot < 0 || slot >= SALUN_LMS_ORDER) return SALUN_EINVAL;
+  if (!guided && scale != 1.0) return SALUN_EINVAL;
+  if ((float)den == 0.0f) return SALUN_EINVAL;
+  if (B == 0 || chw == 0) return SALUN_OK;
+  if (!x || !eps2 || !hist || !x_new) return SALUN_EINVAL;
+  if (hist == x || hist == eps2 || hist == x_new || hist == x_in) return SALUN_EINVAL;
+  if (x_in && (x_in == x || x_in == eps2 || x_in == x_new)) return SALUN_EINVAL;
+  if (chw > ((int64_t)1 << 40) / B) return SALUN_EINVAL;
+  const int64_t n = B * chw;
+  const float *eu = guided ? eps2 : nullptr;   // rows [0, B): unconditional
+  const float *ec = guided ? eps2 + n : eps2;  // rows [B, 2B): conditional
+  const LmsCoef k = {(float)scale, {(float)c0, (float)c1, (float)c2, (float)c3}, (float)den};
+  hipLaunchKernelGGL(k_lms_step, dim3(step_grid(n)), dim3(SALUN_BLOCK), 0, salun_hip_stream(stream), x, eu, ec, k, hist,
+                     slot, order, x_new, x_in, n);
   SALUN_LAUNCH_CHECK();
   return SALUN_OK;
 }

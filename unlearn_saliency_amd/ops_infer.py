@@ -60,6 +60,60 @@ def conv2d_infer(x: torch.Tensor, w: torch.Tensor, scale: Optional[torch.Tensor]
     return out.view(N, K, P, Q)
 
 
+def conv2d_infer_up2_route(N, C, H, W, K, R=3, stride=1, pad=1, P=None, Q=None,
+                           tile: int = _lib.SALUN_INFER_TILE_AUTO) -> Optional[str]:
+    """The label of the plan conv2d_infer_up2 would run on a STORED [N, C, H, W] input, or None where it refuses."""
+    P = conv_out_size(2 * H, R, stride, pad) if P is None else P
+    Q = conv_out_size(2 * W, R, stride, pad) if Q is None else Q
+    buf = ctypes.create_string_buffer(96)
+    rc = _lib.lib().salun_conv2d_infer_up2_route(N, C, H, W, K, R, stride, pad, P, Q, tile, buf, 96)
+    if rc == _lib.SALUN_EINVAL:
+        return None
+    check(rc, "salun_conv2d_infer_up2_route")
+    return buf.value.decode()
+
+
+def conv2d_infer_up2(x: torch.Tensor, w: torch.Tensor, scale: Optional[torch.Tensor] = None,
+                     shift: Optional[torch.Tensor] = None, addend: Optional[torch.Tensor] = None, relu: bool = False,
+                     out: Optional[torch.Tensor] = None, tile: int = _lib.SALUN_INFER_TILE_AUTO, stride: int = 1,
+                     pad: int = 1) -> torch.Tensor:
+    """act(conv(up2(x), w) * scale[k] + shift[k] + addend) with up2 = nearest-neighbour 2x, which is never written:
+    x [N, C, H, W], w [K, C, 3, 3] -> [N, K, 2H, 2W].  One launch.  (stride and pad exist so that a refusal can be asked
+    for; the kernel serves stride 1.)"""
+    N, C, H, W = (int(v) for v in x.shape)
+    K, Cw, R, S = (int(v) for v in w.shape)
+    if Cw != C or R != S:
+        raise ValueError(f"conv2d_infer_up2: weight {tuple(w.shape)} does not fit x {tuple(x.shape)}")
+    P, Q = conv_out_size(2 * H, R, stride, pad), conv_out_size(2 * W, R, stride, pad)
+    if out is None:
+        out = torch.empty((N, K, P, Q), dtype=torch.float32, device=x.device)
+    elif out.numel() != N * K * P * Q:
+        raise ValueError("conv2d_infer_up2: out has the wrong size")
+    if addend is not None and addend.numel() != out.numel():
+        raise ValueError("conv2d_infer_up2: addend has the wrong size")
+    check(_lib.lib().salun_conv2d_infer_up2(_dev(x, torch.float32, "x"), _dev(w, torch.float32, "w"),
+                                            _dev(scale, torch.float32, "scale", True),
+                                            _dev(shift, torch.float32, "shift", True),
+                                            _dev(addend, torch.float32, "addend", True), _dev(out, torch.float32, "out"),
+                                            N, C, H, W, K, R, stride, pad, P, Q, int(bool(relu)), tile, _stream()),
+          "salun_conv2d_infer_up2")
+    return out.view(N, K, P, Q)
+
+
+def decoded_to_u8(x: torch.Tensor, C: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x fp32 [B, Cp, H, W] in [-1, 1] -> uint8 [B, H, W, C] = round(clamp(x / 2 + 0.5, 0, 1) * 255) of its first C
+    channels (default: all), half to even, NaN -> 0."""
+    B, Cp, H, W = (int(v) for v in x.shape)
+    C = Cp if C is None else int(C)
+    if out is None:
+        out = torch.empty((B, H, W, C), dtype=torch.uint8, device=x.device)
+    elif out.numel() != B * H * W * C:
+        raise ValueError("decoded_to_u8: out has the wrong size")
+    check(_lib.lib().salun_decoded_to_u8(_dev(x, torch.float32, "x"), Cp, C, c_int64(H * W), c_int64(B),
+                                         _dev(out, torch.uint8, "out"), _stream()), "salun_decoded_to_u8")
+    return out.view(B, H, W, C)
+
+
 def maxpool3x3s2(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """F.max_pool2d(x, 3, 2, 1) of x [N, C, H, W] -> [N, C, (H+1)/2, (W+1)/2]."""
     N, C, H, W = (int(v) for v in x.shape)

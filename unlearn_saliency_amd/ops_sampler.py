@@ -120,3 +120,37 @@ def ldm_ddim_step(x: torch.Tensor, eps: torch.Tensor, scale: float, c_s1m: float
                                          _dev(out, torch.float32, "out"), f(x0, "x0"), c_int64(B), c_int64(chw),
                                          _stream()), "salun_ldm_ddim_step")
     return out
+
+
+LMS_ORDER = _lib.SALUN_LMS_ORDER
+
+
+def lms_step(x: torch.Tensor, eps: torch.Tensor, scale: float, hist: torch.Tensor, slot: int, coeffs, den: float,
+             out: Optional[torch.Tensor] = None, x_in: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One step of the linear multistep sampler (salun_lms_step; SD/lms.py).  `eps` with 2B rows is the output of one
+    batched U-Net pass (rows [0, B) unconditional, [B, 2B) conditional, read in place); with B rows there is no guidance
+    and `scale` must be 1.  `hist` [LMS_ORDER, *x.shape] is the ring of derivatives: this step's goes to `slot`, and
+    `coeffs` (1 to LMS_ORDER host floats, newest derivative first) weigh slot, slot - 1, ...  `x_in`, when given, receives
+    x_new / den in each of its eps.shape[0] / B row blocks: the input of the next pass.  `out` may be `x`."""
+    B, chw = _rows(x)
+    if eps.shape[0] not in (B, 2 * B) or eps.shape[1:] != x.shape[1:]:
+        raise ValueError(f"eps {tuple(eps.shape)} is neither x {tuple(x.shape)} nor its two-fold batch")
+    guided = B > 0 and eps.shape[0] == 2 * B
+    c = [float(v) for v in coeffs]
+    if not 1 <= len(c) <= LMS_ORDER:
+        raise ValueError(f"lms_step: {len(c)} coefficients, the order is 1 to {LMS_ORDER}")
+    if tuple(hist.shape) != (LMS_ORDER,) + tuple(x.shape):
+        raise ValueError(f"hist {tuple(hist.shape)} must be {(LMS_ORDER,) + tuple(x.shape)}")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape:
+        raise ValueError(f"out {tuple(out.shape)} does not match x {tuple(x.shape)}")
+    if x_in is not None and x_in.shape != eps.shape:
+        raise ValueError(f"x_in {tuple(x_in.shape)} does not match eps {tuple(eps.shape)}")
+    c4 = c + [0.0] * (LMS_ORDER - len(c))
+    check(_lib.lib().salun_lms_step(_dev(x, torch.float32, "x"), _dev(eps, torch.float32, "eps"), int(guided),
+                                    c_double(scale), _dev(hist, torch.float32, "hist"), int(slot), len(c),
+                                    c_double(c4[0]), c_double(c4[1]), c_double(c4[2]), c_double(c4[3]), c_double(den),
+                                    _dev(out, torch.float32, "out"), _dev(x_in, torch.float32, "x_in", True),
+                                    c_int64(B), c_int64(chw), _stream()), "salun_lms_step")
+    return out

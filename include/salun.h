@@ -1225,6 +1225,45 @@ int salun_lms_step(const float *x /*dev*/, const float *eps2 /*dev, 2B or B rows
                    double c3, double den, float *x_new /*dev*/, float *x_in /*dev, 2B or B rows, or NULL*/, int64_t B,
                    int64_t chw, salun_stream_t stream);
 
+/* ----------------------------------------------------------------- K29 --
+ * The CLIP text encoder of Stable Diffusion v1 (csrc/salun_clip_text.hip).  Replaces, together with the
+ * K15 GEMM for the Linear layers, transformers' CLIPTextModel as SD/ldm/modules/encoders/modules.py
+ * `FrozenCLIPEmbedder.forward` calls it.  All four are fp32, forward only and deterministic; the rounding points of each
+ * are listed in the header comment of the source file.
+ *
+ * salun_clip_embed: x[b, t, :] = tok[ids[b, t], :] + pos[t, :] for ids [B, T] (int64), tok [V, W], pos [>= T, W]: one
+ * fp32 add per element.  The caller validates the ids (they come from the host tokenizer); an id outside [0, V) reads
+ * nothing and writes a row of NaN.
+ * SALUN_EINVAL (nothing is written): B or T < 1, W < 4 or no multiple of 4, V < 1, a NULL pointer, tok, pos or x off
+ * 16-byte alignment, ids off 8-byte alignment.
+ *
+ * salun_ln_f32_forward: y = (x - mean) / sqrt(var + eps) * gamma + beta over the last dimension of x [rows, W]; biased
+ * variance from the centred values (two passes over registers), fp32 statistics.  W a multiple of 4, 4 <= W <= 2048.
+ * y must not overlap x.
+ * SALUN_EINVAL (nothing is written): rows < 1, W outside the domain, eps < 0 or NaN, a NULL pointer, x or y off 16-byte
+ * alignment.
+ *
+ * salun_attn_causal_f32: o = softmax(scale q k^T + causal mask) v per (batch, head), head width D = SALUN_CLIP_ATTN_D,
+ * 1 <= T <= SALUN_CLIP_ATTN_MAX_T.  Element (b, t, h, d) of q is qkv[(b T + t) ld + q_off + D h + d], of k and v the
+ * same at k_off / v_off (the fused projection buffer [B T, 3 W] has ld = 3 W and offsets 0, W, 2 W); o is written at
+ * o[(b T + t) ld_o + D h + d].  Key j > t has weight exactly 0.  o must not overlap qkv.
+ * SALUN_EINVAL (nothing is written): D != SALUN_CLIP_ATTN_D, T outside its range, B or H < 1, an offset or a leading
+ * dimension that is negative, no multiple of 4 or too small for H D columns, a NULL pointer, qkv or o off 16-byte
+ * alignment.
+ *
+ * salun_quick_gelu: x <- x * sigmoid(1.702 x) in place over n floats (any n; the float4 route needs 16-byte alignment,
+ * the scalar route is taken otherwise).
+ * SALUN_EINVAL: n < 0, NULL x with n > 0, x off 4-byte alignment. */
+#define SALUN_CLIP_ATTN_MAX_T 128
+#define SALUN_CLIP_ATTN_D 64
+int salun_clip_embed(const int64_t *ids /*dev, B*T*/, const float *tok /*dev, V*W*/, const float *pos /*dev, T*W*/,
+                     float *x /*dev, B*T*W*/, int64_t B, int T, int W, int64_t V, salun_stream_t stream);
+int salun_ln_f32_forward(const float *x /*dev*/, const float *gamma /*dev, W*/, const float *beta /*dev, W*/,
+                         float *y /*dev*/, int64_t rows, int W, double eps, salun_stream_t stream);
+int salun_attn_causal_f32(const float *qkv /*dev*/, float *o /*dev*/, int B, int H, int T, int D, int64_t ld, int q_off,
+                          int k_off, int v_off, int64_t ld_o, double scale, salun_stream_t stream);
+int salun_quick_gelu(float *x /*dev, n*/, int64_t n, salun_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,7 +21,7 @@ ops (any device, any dtype): it is the yardstick of the tests and of tools/vae_b
     that (64 x 64 latents = 4096 tokens take the library route; gemm.py measured it faster there).
 The plan copies the weights it pads: re-plan after loading other weights into the model.
 
-Out of scope: the decoder, the CLIP text encoder, bf16.
+Out of scope: bf16 (the decoder is below; the CLIP text encoder is SD/clip_text.py).
 """
 from __future__ import annotations
 

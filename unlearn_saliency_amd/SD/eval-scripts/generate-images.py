@@ -12,8 +12,11 @@ loads the Diffusers twin next to it); when "SD" is in the model name the untouch
 
 Additions:
     --ckpt_path FILE   SD-v1 checkpoint: the VAE decoder and the base U-Net       --config_path FILE  its YAML
-    --contexts FILE    torch.save'd dict {prompt: (1, 77, 768) tensor} holding "" and every prompt of the CSV (the CLIP
-                       text encoder is outside this package's scope, SD/train-scripts/_common.py)
+    --contexts FILE    torch.save'd dict {prompt: (1, 77, 768) tensor} holding "" and every prompt of the CSV
+                       (SD/train-scripts/encode_prompts.py writes one)
+    --tokenizer DIR    instead of --contexts: the folder with the CLIP tokenizer's vocab.json and merges.txt; the prompts
+                       are encoded here, by the text model of --ckpt_path (SD/clip_text.py: K29 and the K15 GEMM); with
+                       --synthetic by a seeded two-layer text model of the U-Net's context width
     --sampler lms|ddim lms (default) or SD/ddim.py's DDIM chain with till_T = None
     --rounds N         rounds per row (default 10, as the reference)              --decode_batch N  latents per decode
     --bf16             the U-Net in the bf16 configuration (the decoder stays fp32)
@@ -32,6 +35,9 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 UNET_PREFIX = "model.diffusion_model."
+NO_CONTEXTS = ("give --contexts FILE (context embeddings of \"\" and every prompt) or --synthetic: the text encoder runs "
+               "only where it is asked for.  --tokenizer DIR names the folder with the CLIP tokenizer's vocab.json and "
+               "merges.txt; with it and --ckpt_path the script encodes its own prompts (SD/clip_text.py).")
 
 
 def build_parser():
@@ -50,6 +56,8 @@ def build_parser():
     parser.add_argument("--config_path", type=str, default="configs/stable-diffusion/v1-inference.yaml")
     parser.add_argument("--contexts", type=str, default=None,
                         help='file with the context embeddings: {prompt: (1, 77, ctx) tensor} holding "" and every prompt')
+    parser.add_argument("--tokenizer", type=str, default=None,
+                        help="folder with the CLIP tokenizer's vocab.json and merges.txt: encode the prompts here")
     parser.add_argument("--bf16", action="store_true", help="the U-Net in the bf16 configuration")
     parser.add_argument("--sampler", choices=("lms", "ddim"), default="lms")
     parser.add_argument("--rounds", type=int, default=10, help="rounds per row (the reference makes 10)")
@@ -124,6 +132,10 @@ def load_contexts(args, prompts, model, device):
     import torch
     if args.contexts:
         contexts = torch.load(args.contexts, map_location=device, weights_only=False)
+    elif args.tokenizer:
+        from unlearn_saliency_amd.SD import clip_text
+        synthetic = clip_text.synthetic_config(model.model.diffusion_model.context_dim, 0) if args.synthetic else None
+        contexts = clip_text.contexts_for(prompts, args.tokenizer, args.ckpt_path, device, synthetic, args.seed)
     elif args.synthetic:
         import zlib
         dim = model.model.diffusion_model.context_dim
@@ -132,8 +144,7 @@ def load_contexts(args, prompts, model, device):
             (args.seed << 32) + zlib.crc32(p.encode())))
         contexts = {p: draw(p).to(device) for p in [""] + sorted(set(prompts))}
     else:
-        raise SystemExit("give --contexts FILE (context embeddings of \"\" and every prompt) or --synthetic: the text "
-                         "encoder is outside this package's scope (SD/train-scripts/_common.py)")
+        raise SystemExit(NO_CONTEXTS)
     for p in [""] + prompts:
         if p not in contexts:
             raise SystemExit(f"--contexts: no embedding of the prompt `{p}`")
@@ -145,6 +156,8 @@ def generate_images(args):
     from PIL import Image
     from unlearn_saliency_amd.SD.ddim import DDIMSampler
     from unlearn_saliency_amd.SD.lms import LMSSampler
+    if not (args.contexts or args.tokenizer or args.synthetic):
+        raise SystemExit(NO_CONTEXTS)
     if not torch.cuda.is_available():
         raise SystemExit("generate-images needs a ROCm device (no CPU fallback for the measured path)")
     device = args.device if ":" in args.device or not args.device.isdigit() else f"cuda:{int(args.device)}"

@@ -3,10 +3,11 @@
 :1121 apply_model, :1286-1319 p_losses) that the SalUn scripts call — schedule buffers, `q_sample`,
 `apply_model`, `shared_step`, `get_input` — around the U-Net of unet.py.
 
-The frozen first stage (AutoencoderKL) and text encoder (CLIP) are outside the hot-path scope (SURVEY.md §2 S4;
-their weights are not available offline), so batches carry *latents and context embeddings* directly:
-``{"z": (B,4,64,64) fp32, "c": (B,77,768) fp32}``.  A caller that has the encoders can pass
-`first_stage` / `cond_stage` callables and feed the reference's ``{"jpg": ..., "txt": ...}`` batches.
+The frozen first stage (AutoencoderKL) and text encoder (CLIP) are not part of the measured step,
+so batches carry *latents and context embeddings* directly:
+``{"z": (B,4,64,64) fp32, "c": (B,77,768) fp32}``.  A caller that wants the reference's
+``{"jpg": ..., "txt": ...}`` batches passes `first_stage` / `cond_stage` callables: `EncoderPlan.first_stage(seed)` of
+autoencoder.py and `TextPlan.cond_stage(tokenizer)` of clip_text.py.
 Parameter names keep the reference's prefix (`model.diffusion_model.*`), which is what the mask-key
 rewrite in the scripts (`n.split("model.diffusion_model.")[-1]`, random_label.py:135) relies on.
 """

@@ -2,9 +2,10 @@
 the reference's parsers (names, types, defaults; pinned by tests/golden/cli.json) and the batch sources.
 
 The reference's scripts build their loaders from image folders through the frozen VAE / CLIP encoders
-(SD/train-scripts/dataset.py).  The CLIP text encoder is outside this package's scope (its tokenizer's vocabulary is a
-download); the VAE encoder is SD/autoencoder.py, and encode_images.py runs it once over an image manifest.  These
-front-ends take the pre-encoded batches it writes:
+(SD/train-scripts/dataset.py).  The CLIP text encoder is SD/clip_text.py (encode_prompts.py runs it once over a list of
+prompts; the tokenizer's two vocabulary files are the user's to name with --tokenizer DIR); the VAE encoder is
+SD/autoencoder.py, and encode_images.py runs it once over an image manifest.  These front-ends take the pre-encoded
+batches it writes:
 
     --latents FILE    torch.save'd dict {"forget": [(z, c_forget, c_other), ...], "remain": [(z, c), ...]} with
                       z (B,4,64,64) latents and c (B,77,768) CLIP contexts (c_other = the empty-prompt context for
@@ -59,5 +60,4 @@ def batches(args, device, kinds, model=None):
             out[k] = [tuple([mk(B, cin, hw, hw)] + [mk(B, 77, ctx) for _ in range(n - 1)]) for _ in range(args.synthetic)]
         return out
     raise SystemExit("give --latents FILE (pre-encoded batches; encode_images.py writes one from an image manifest and a "
-                     "--contexts file) or --synthetic N: the text encoder of the reference's loaders is outside this "
-                     "package's scope (SD/train-scripts/_common.py)")
+                     "--contexts file or a --tokenizer folder) or --synthetic N (SD/train-scripts/_common.py)")

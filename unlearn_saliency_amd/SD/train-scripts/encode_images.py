@@ -9,8 +9,10 @@ kernel.  The file is exactly the dict `_common.batches` loads:
     {"forget": [(z, c_forget, c_other), ...], "remain": [(z, c), ...]}     z already scaled by 0.18215
 
     --manifest FILE   CSV rows  split,path,prompt[,other_prompt]  with split in forget | remain (SD/images.py)
-    --contexts FILE   torch.save'd dict {prompt: (1, 77, ctx) tensor}, as train-esd.py reads it: the CLIP text encoder
-                      stays outside this package's scope (its tokenizer's vocabulary is a download)
+    --contexts FILE   torch.save'd dict {prompt: (1, 77, ctx) tensor}, as train-esd.py reads it (encode_prompts.py
+                      writes one)
+    --tokenizer DIR   instead: the folder with the CLIP tokenizer's vocab.json and merges.txt; the manifest's prompts are
+                      encoded here by the text model of --ckpt_path (SD/clip_text.py: K29 and the K15 GEMM)
     --synthetic N     seeded encoder weights, `fill_u8` images and random contexts: N batches per split
 
 A difference from the reference, by construction: a file freezes ONE posterior draw per image (keyed by --seed and
@@ -29,6 +31,8 @@ def build_parser():
     parser = argparse.ArgumentParser(prog="EncodeImages", description="Encode images to SD latents with the frozen VAE encoder")
     parser.add_argument("--manifest", type=str, default=None, help="CSV: split,path,prompt[,other_prompt]")
     parser.add_argument("--contexts", type=str, default=None, help="file with {prompt: (1, 77, ctx) tensor}")
+    parser.add_argument("--tokenizer", type=str, default=None,
+                        help="folder with the CLIP tokenizer's vocab.json and merges.txt: encode the prompts here")
     parser.add_argument("--ckpt_path", type=str, default="models/ldm/sd-v1-4-full-ema.ckpt",
                         help="SD-v1 CompVis checkpoint (or a bare autoencoder state dict)")
     parser.add_argument("--image_size", type=int, default=512)
@@ -45,6 +49,11 @@ def build_parser():
     return parser
 
 
+NO_SOURCE = ("give --manifest FILE and --contexts FILE, or --synthetic N.  --tokenizer DIR names the folder with the CLIP "
+             "tokenizer's vocab.json and merges.txt; with it and --ckpt_path the script encodes its own prompts "
+             "(SD/clip_text.py).")
+
+
 def _ddconfig(arg):
     if arg is None:
         return None
@@ -59,6 +68,8 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.batch_size < 1:
         raise SystemExit("--batch_size must be at least 1")
+    if args.synthetic <= 0 and (not args.manifest or not (args.contexts or args.tokenizer)):
+        raise SystemExit(NO_SOURCE)
     device = _common.device_of(args.device)
     from unlearn_saliency_amd import ops
     from unlearn_saliency_amd.SD import images
@@ -76,10 +87,13 @@ def main(argv=None):
                     for p in sorted({r.prompt for r in rows} | {""})}
         pixels = lambda i, r: ops.fill_u8(S * S * 3, args.seed * 1000003 + i, device).view(S, S, 3)
     else:
-        if not args.manifest or not args.contexts:
-            raise SystemExit("give --manifest FILE and --contexts FILE, or --synthetic N")
         rows = images.read_manifest(args.manifest)
-        contexts = torch.load(args.contexts, map_location="cpu", weights_only=False)
+        if args.contexts:
+            contexts = torch.load(args.contexts, map_location="cpu", weights_only=False)
+        else:
+            from unlearn_saliency_amd.SD import clip_text
+            wanted = [p for r in rows for p in (r.prompt, r.other_prompt) if p is not None]
+            contexts = clip_text.contexts_for(wanted, args.tokenizer, args.ckpt_path, device, batch=max(B, 8))
         try:
             images.check_prompts(rows, contexts)
         except KeyError as e:

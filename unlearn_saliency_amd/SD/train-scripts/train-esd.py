@@ -2,9 +2,12 @@
 SD/train-scripts/train-esd.py:381-511 in front of `unlearn_saliency_amd.SD.train_scripts.train_esd`: Erased Stable
 Diffusion, and with `--mask_path` ESD restricted to a saliency mask written by generate_mask.py.
 
-The text encoder is outside this package's scope (_common.py), so the prompts' context embeddings come from a file:
+The prompts' context embeddings come from a file or from the text encoder of SD/clip_text.py:
 
     --contexts FILE   torch.save'd dict {prompt: (1, 77, ctx) tensor} holding "" and every word of the prompt
+                      (encode_prompts.py writes one)
+    --tokenizer DIR   instead: the folder with the CLIP tokenizer's vocab.json and merges.txt; "" and the words are
+                      encoded here by the text model of --ckpt_path (K29 and the K15 GEMM)
     --synthetic N     (any N > 0) random contexts for "" and each word (benchmarks / smoke runs)
 
 Reference quirks kept visible rather than reproduced: its `--lr` is declared `type=int` (so any `--lr 1e-5` on the
@@ -45,9 +48,25 @@ def build_parser():
     return parser
 
 
+def full_parser():
+    """build_parser() is the table pinned against the reference's (tests/golden/cli_sd_baselines.json: its flags plus
+    the batch-source additions); the command line adds the text encoder's flag to it."""
+    parser = build_parser()
+    parser.add_argument("--tokenizer", type=str, default=None,
+                        help="folder with the CLIP tokenizer's vocab.json and merges.txt: encode the words here")
+    return parser
+
+
+NO_CONTEXTS = ("give --contexts FILE (context embeddings of \"\" and every word) or --synthetic N: the text encoder runs "
+               "only where it is asked for.  --tokenizer DIR names the folder with the CLIP tokenizer's vocab.json and "
+               "merges.txt; with it and --ckpt_path the script encodes its own prompts (SD/clip_text.py).")
+
+
 def main(argv=None):
     import torch
-    args = build_parser().parse_args(argv)
+    args = full_parser().parse_args(argv)
+    if not (args.contexts or args.tokenizer or args.synthetic > 0):
+        raise SystemExit(NO_CONTEXTS)
     devices = [_common.device_of(d.strip()) for d in args.devices.split(",")]
     from unlearn_saliency_amd.SD import train_scripts as TS
     model = TS.setup_model(args.config_path, args.ckpt_path, devices[0], bf16=args.bf16,
@@ -55,13 +74,15 @@ def main(argv=None):
     _, words = TS.esd_words(args.prompt, args.seperator)
     if args.contexts:
         contexts = torch.load(args.contexts, map_location=devices[0], weights_only=False)
+    elif args.tokenizer:
+        from unlearn_saliency_amd.SD import clip_text
+        contexts = clip_text.contexts_for(words, args.tokenizer, args.ckpt_path, devices[0])
     elif args.synthetic > 0:
         g = torch.Generator(device=devices[0]).manual_seed(0)
         dim = model.model.diffusion_model.context_dim
         contexts = {w: torch.randn(1, 77, dim, device=devices[0], generator=g) for w in [""] + words}
     else:
-        raise SystemExit("give --contexts FILE (context embeddings of \"\" and every word) or --synthetic N: the text "
-                         "encoder is outside this package's scope (SD/train-scripts/_common.py)")
+        raise SystemExit(NO_CONTEXTS)
     model, losses = TS.train_esd(args.prompt, args.train_method, args.start_guidance, args.negative_guidance,
                                  args.iterations, args.lr, args.config_path, args.ckpt_path, args.mask_path,
                                  args.diffusers_config_path, devices, args.seperator, args.image_size, args.ddim_steps,

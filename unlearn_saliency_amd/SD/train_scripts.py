@@ -445,8 +445,8 @@ def train_esd(prompt, train_method, start_guidance, negative_guidance, iteration
     loss = MSE(e_n, e_0 - negative_guidance * (e_p - e_0)) with its gradient in one launch (ops.esd_loss); fused masked
     Adam over `train_method`'s parameters AND the saliency mask.
 
-    `contexts` maps a prompt string to its (1, 77, ctx) context embedding and must hold "" and every word (the text
-    encoder is out of scope, SD/train-scripts/_common.py).  `devices` is accepted for the reference's signature; both
+    `contexts` maps a prompt string to its (1, 77, ctx) context embedding and must hold "" and every word
+    (SD/clip_text.py: contexts_for computes it; encode_prompts.py writes it to a file).  `devices` is accepted for the reference's signature; both
     models live on devices[0] — one MI355X holds the two U-Nets many times over, so the reference's second GPU is not
     needed, and with a batch of one latent there is nothing to shard over more devices (no multi-GPU ESD).
     `save`: write the reference's loss.txt / periodic checkpoints under

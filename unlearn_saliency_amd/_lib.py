@@ -75,6 +75,8 @@ SALUN_U8_NORM_MAX_C = 4
 SALUN_GN_SPLIT_FLUSH = 16
 SALUN_DECODED_U8_MAX_C = 4
 SALUN_LMS_ORDER = 4
+SALUN_CLIP_ATTN_MAX_T = 128
+SALUN_CLIP_ATTN_D = 64
 
 # name -> (restype, argtypes); mirrors include/salun.h one to one
 # (tests/test_cabi.py checks this table against the header and the .so).
@@ -262,6 +264,11 @@ SIGNATURES = {
     "salun_decoded_to_u8": (c_int, [c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p]),
     "salun_lms_step": (c_int, [c_void_p, c_void_p, c_int, c_double, c_void_p, c_int, c_int] + [c_double] * 5 +
                        [c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+    "salun_clip_embed": (c_int, [c_void_p] * 4 + [c_int64, c_int, c_int, c_int64, c_void_p]),
+    "salun_ln_f32_forward": (c_int, [c_void_p] * 4 + [c_int64, c_int, c_double, c_void_p]),
+    "salun_attn_causal_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_int64, c_int, c_int, c_int, c_int64, c_double,
+                                                                         c_void_p]),
+    "salun_quick_gelu": (c_int, [c_void_p, c_int64, c_void_p]),
 }
 
 _lib = None

@@ -1106,6 +1106,37 @@ int salun_conv2d_infer_up2(const float *x /*dev, N*C*H*W*/, const float *w /*dev
 int salun_conv2d_infer_up2_route(int N, int C, int H, int W, int K, int R, int stride, int pad, int P, int Q, int tile,
                                  char *buf, size_t buflen);
 
+/* ----------------------------------------------------------------- K30 --
+ * Forward-only fp32 POINTWISE convolution (1 x 1, stride 1, no padding) with K27's epilogue
+ * (csrc/salun_conv1x1_infer.hip).  Replaces, in eval mode, the conv1 / conv3 / stride-1 downsample
+ * convolutions of  torchvision.models.resnet50  (SD/eval-scripts/imageclassify.py:24-26)  with their BatchNorm,
+ * residual add and ReLU.
+ *   y[n,k,g] = act( (sum_c w[k,c] x[n,c,g]) * scale[k] + shift[k] + addend[n,k,g] ),   g in [0, HW)
+ * x [N, C, HW], w [K, C], y and addend [N, K, HW], scale and shift [K]; scale, shift and addend may each be NULL; relu
+ * and the epilogue (each operation rounded by itself, in the order written) are salun_conv2d_infer's.
+ * Reduction: ONE fp32 FMA chain per output element over c in ascending order on v_mfma_f32_32x32x2_f32, no split over
+ * C - the chain salun_conv2d_infer runs for R == 1, so the two return the same bits and a caller may route a layer to
+ * either.  (A reduction tail is padded with (+0)(+0) products, as K27's generic order pads.)
+ * Domain: N >= 1, HW >= 1, N HW <= 2^40; C a multiple of 8, 8 <= C <= 65536; K a multiple of 32, 32 <= K <= 65536.
+ * Indexing is 64-bit.  Tiles span images; the last pixel tile and a channel tile K does not fill are masked.
+ * Staging: x is read as 16-byte row segments where HW % 4 == 0 and x and y are 16-byte aligned, else 4 bytes at a
+ * time; w as 16-byte segments where w is 16-byte aligned.  Every path gives the same bits.
+ * `tile`: SALUN_INFER_TILE_*, as salun_conv2d_infer (same AUTO rule); every tile gives the same bits.
+ * One launch, no workspace, no atomics: the same inputs give the same bits, and an image's output does not depend on
+ * the rest of the batch.
+ * SALUN_EINVAL (nothing is written): anything outside the domain, a NULL x, w or y, addend == y, x == y, a pointer off
+ * 4-byte alignment.
+ * salun_conv1x1_infer_route: the label of the plan a call would run, from the plan function the launch uses; touches
+ * no device.  aligned16: x and y are 16-byte aligned; w_aligned16: w is.
+ * pw/<pixels>x<channels>/<vec16|vec4|scalar>/B<workgroups>; vec16: 16-byte loads of x and w, vec4: 4-byte loads of x,
+ * scalar: 4-byte loads of both.  SALUN_ENOSPC: buf too short. */
+int salun_conv1x1_infer(const float *x /*dev, N*C*HW*/, const float *w /*dev, K*C*/,
+                        const float *scale /*dev, K, or NULL*/, const float *shift /*dev, K, or NULL*/,
+                        const float *addend /*dev, N*K*HW, or NULL*/, float *y /*dev, N*K*HW*/, int N, int C, int64_t HW,
+                        int K, int relu, int tile, salun_stream_t stream);
+int salun_conv1x1_infer_route(int N, int C, int64_t HW, int K, int tile, int aligned16, int w_aligned16, char *buf,
+                              size_t buflen);
+
 /* MaxPool2d(kernel_size=3, stride=2, padding=1), forward only (csrc/salun_pool.hip, beside K24).
  * Replaces  resnet34().maxpool  (DDPM/classifier_evaluation.py:135).
  * x [NC, H, W] (contiguous), y [NC, (H+1)/2, (W+1)/2], any H, W >= 1.  Padding acts as -inf.  Selection is that of
@@ -1130,6 +1161,16 @@ int salun_u8_norm_table(const float *mean /*host, C*/, const float *std /*host, 
 int salun_u8_to_chw_norm(const uint8_t *src /*dev, B*H*W*C*/, const float *table /*dev, 256*C*/,
                          float *dst /*dev, B*C*H*W*/, int64_t B, int H, int W, int C, salun_stream_t stream);
 
+/* salun_u8_to_chw_norm of a WINDOW of the source: transforms.CenterCrop then ToTensor + Normalize without a copy of the
+ * crop.  Replaces the crop and normalise of  ResNet50_Weights.DEFAULT.transforms()  (SD/eval-scripts/imageclassify.py:27).
+ * src [B, H, W, C] uint8, dst [B, C, OH, OW] fp32:  dst[b,c,i,j] = table[c][src[b, top + i, left + j, c]], the table of
+ * salun_u8_norm_table.  With top == left == 0, OH == H, OW == W it writes what salun_u8_to_chw_norm writes.
+ * SALUN_EINVAL (nothing is written): as salun_u8_to_chw_norm; a window that does not lie inside the image (top or
+ * left < 0, OH or OW < 1, top + OH > H, left + OW > W). */
+int salun_u8_crop_to_chw_norm(const uint8_t *src /*dev, B*H*W*C*/, const float *table /*dev, 256*C*/,
+                              float *dst /*dev, B*C*OH*OW*/, int64_t B, int H, int W, int C, int top, int left, int OH,
+                              int OW, salun_stream_t stream);
+
 /* The evaluation head (csrc/salun_cls_head.hip, beside K23): pool -> fc -> softmax as salun_cls_head_forward (same
  * statements, same rounding points), then the figures of DDPM/classifier_evaluation.py:22-36 for ONE label shared by
  * the whole batch.  Replaces  model.avgpool / model.fc  and  validate()'s  argmax / softmax / log / sums.
@@ -1149,6 +1190,18 @@ int salun_cls_head_eval(const float *x /*dev, B*C*HW*/, const float *w /*dev, K*
                         double *entropy_sum /*dev or NULL*/, double *prob_sum /*dev or NULL*/,
                         int64_t *hits /*dev or NULL*/, int64_t *count /*dev or NULL*/, int64_t B, int C, int HW, int K,
                         int zero_safe, void *ws /*dev*/, size_t ws_bytes, salun_stream_t stream);
+
+/* The k largest entries of every row, sorted, with their indices (csrc/salun_row_topk.hip).
+ * Replaces  torch.topk(probs, topk)  (SD/eval-scripts/imageclassify.py:66) on the p of salun_cls_head_eval.
+ * p [B, K] fp32, values [B, k] fp32 (the entries' own bits), indices [B, k] int64; 1 <= K <= SALUN_CLS_HEAD_MAX_K,
+ * 1 <= k <= K, 1 <= B < 2^31.
+ * THE ORDER: a larger value comes first; a NaN ranks above every number; equal values - NaNs among themselves and -0
+ * with +0 included - go by ascending index.  That is torch.topk's result wherever a row has no ties; on ties torch
+ * promises nothing and this does.
+ * One launch, one workgroup per row, no atomics, no workspace: deterministic.
+ * SALUN_EINVAL (nothing is written): a size outside the limits, a NULL pointer, a pointer off its element's alignment. */
+int salun_row_topk(const float *p /*dev, B*K*/, float *values /*dev, B*k*/, int64_t *indices /*dev, B*k*/, int64_t B,
+                   int K, int k, salun_stream_t stream);
 
 /* ----------------------------------------------------------------- K28 --
  * GroupNorm (+ SiLU) forward for groups too large for one workgroup (csrc/salun_gn_split.hip).

@@ -261,6 +261,10 @@ SIGNATURES = {
                                            c_double, c_int, c_void_p, c_void_p]),
     "salun_conv2d_infer_up2": (c_int, [c_void_p] * 6 + [c_int] * 12 + [c_void_p]),
     "salun_conv2d_infer_up2_route": (c_int, [c_int] * 11 + [ctypes.c_char_p, c_size_t]),
+    "salun_conv1x1_infer": (c_int, [c_void_p] * 6 + [c_int, c_int, c_int64, c_int, c_int, c_int, c_void_p]),
+    "salun_conv1x1_infer_route": (c_int, [c_int, c_int, c_int64, c_int, c_int, c_int, c_int, ctypes.c_char_p, c_size_t]),
+    "salun_u8_crop_to_chw_norm": (c_int, [c_void_p, c_void_p, c_void_p, c_int64] + [c_int] * 7 + [c_void_p]),
+    "salun_row_topk": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "salun_decoded_to_u8": (c_int, [c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p]),
     "salun_lms_step": (c_int, [c_void_p, c_void_p, c_int, c_double, c_void_p, c_int, c_int] + [c_double] * 5 +
                        [c_void_p, c_void_p, c_int64, c_int64, c_void_p]),

@@ -1,5 +1,5 @@
-"""Inference convolution, pool and image normalisation on K27 and its companions (csrc/salun_conv_infer.hip,
-salun_pool.hip, salun_imgnorm.hip).
+"""Inference convolution, pool and image normalisation on K27, K30 and their companions (csrc/salun_conv_infer.hip,
+salun_conv1x1_infer.hip, salun_pool.hip, salun_imgnorm.hip).
 
 Thin callers in the pattern of pool.py: inside the kernels' domain a call is one launch; outside it (a dtype or device
 the kernels do not take, autocast, a filter or stride K27 refuses) the library op runs — LOUDLY: every such call is
@@ -18,7 +18,7 @@ from . import _lib, ops_infer
 
 # calls that went to the library instead of K27 / the pool / the normalise kernel, by reason
 LIBRARY_INFER_CALLS = {"conv_shape": 0, "conv_dtype_or_autocast": 0, "conv_requires_grad": 0, "pool_dtype_or_autocast": 0,
-                       "norm_shape": 0, "conv_up2": 0}
+                       "norm_shape": 0, "conv_up2": 0, "resize_host": 0}
 
 
 def library_infer_calls() -> int:
@@ -72,6 +72,36 @@ def conv_bn_act(x: torch.Tensor, w: torch.Tensor, scale: Optional[torch.Tensor] 
         return _library_conv(x, w, scale, shift, addend, relu, stride, pad, out_size)
     return ops_infer.conv2d_infer(x.contiguous(), w.contiguous(), scale, shift,
                                   None if addend is None else addend.contiguous(), relu, stride, pad, out, tile, out_size)
+
+
+def conv1x1_bn_act(x: torch.Tensor, w: torch.Tensor, scale: Optional[torch.Tensor] = None,
+                   shift: Optional[torch.Tensor] = None, addend: Optional[torch.Tensor] = None, relu: bool = False,
+                   out: Optional[torch.Tensor] = None, tile: int = _lib.SALUN_INFER_TILE_AUTO) -> torch.Tensor:
+    """act(conv2d(x, w) * scale[k] + shift[k] + addend) of a 1 x 1 / stride-1 / unpadded w [K, C, 1, 1] on K30, forward
+    only.  Outside K30's domain the call is `conv_bn_act`'s (K27, which returns the same bits, or - counted there - the
+    library); nothing is counted here."""
+    ts = [t for t in (x, w, scale, shift, addend) if t is not None]
+    ok = all(t.is_cuda and t.dtype == torch.float32 for t in ts) and not torch.is_autocast_enabled() and \
+        not (torch.is_grad_enabled() and any(t.requires_grad for t in ts)) and x.dim() == 4 and w.dim() == 4 and \
+        w.shape[2] == 1 and w.shape[3] == 1 and w.shape[1] == x.shape[1] and x.shape[0] >= 1 and \
+        x.shape[2] * x.shape[3] >= 1
+    if ok:
+        N, C, H, W = (int(v) for v in x.shape)
+        ok = ops_infer.conv1x1_infer_route(N, C, H * W, int(w.shape[0]), tile) is not None
+    if not ok:
+        return conv_bn_act(x, w, scale, shift, addend, relu, 1, 0, out, tile)
+    return ops_infer.conv1x1_infer(x.contiguous(), w.contiguous(), scale, shift,
+                                   None if addend is None else addend.contiguous(), relu, out, tile)
+
+
+def u8_crop_to_chw_norm(src: torch.Tensor, table: torch.Tensor, top: int, left: int, OH: int, OW: int,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Normalize(ToTensor(src[:, top:top+OH, left:left+OW])) of uint8 [B, H, W, C] device images; a window outside the
+    image is an error, not a library call."""
+    if not (src.is_cuda and src.dtype == torch.uint8 and src.dim() == 4 and 1 <= src.shape[3] <= _lib.SALUN_U8_NORM_MAX_C):
+        LIBRARY_INFER_CALLS["norm_shape"] += 1
+        return u8_to_chw_norm(src[:, top:top + OH, left:left + OW].contiguous(), table, out)
+    return ops_infer.u8_crop_to_chw_norm(src.contiguous(), table, top, left, OH, OW, out)
 
 
 def maxpool3x3s2(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:

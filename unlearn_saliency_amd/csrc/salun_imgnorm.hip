@@ -52,3 +52,40 @@ SALUN_EXPORT int salun_u8_to_chw_norm(const uint8_t *src, const float *table, fl
   SALUN_LAUNCH_CHECK();
   return SALUN_OK;
 }
+
+// ---- the same operator on a WINDOW of the source: torchvision's preset is resize -> centre crop -> normalise, and the
+// crop is an address offset here, not a copy.  One output pixel per thread, grid-stride; the table is the one above.
+namespace {
+
+__global__ __launch_bounds__(SALUN_BLOCK) void k_u8_crop_to_chw_norm(const uint8_t *__restrict__ src,
+                                                                     const float *__restrict__ table,
+                                                                     float *__restrict__ dst, int64_t pixels, int H, int W,
+                                                                     int C, int top, int left, int OH, int OW) {
+  __shared__ float tab[MAX_C * 256];
+  for (int i = threadIdx.x; i < C * 256; i += SALUN_BLOCK) tab[i] = table[i];
+  __syncthreads();
+  const int64_t OHW = static_cast<int64_t>(OH) * OW;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * SALUN_BLOCK;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * SALUN_BLOCK + threadIdx.x; i < pixels; i += stride) {
+    const int64_t b = i / OHW, hw = i - b * OHW;
+    const int oh = static_cast<int>(hw / OW), ow = static_cast<int>(hw - static_cast<int64_t>(oh) * OW);
+    const uint8_t *s = src + ((b * H + (top + oh)) * W + (left + ow)) * C;
+    float *d = dst + b * C * OHW + hw;
+    for (int c = 0; c < C; ++c) d[c * OHW] = tab[c * 256 + s[c]];
+  }
+}
+
+}  // namespace
+
+SALUN_EXPORT int salun_u8_crop_to_chw_norm(const uint8_t *src, const float *table, float *dst, int64_t B, int H, int W,
+                                           int C, int top, int left, int OH, int OW, salun_stream_t stream) {
+  if (B < 1 || H < 1 || W < 1 || H > (1 << 20) || W > (1 << 20) || C < 1 || C > MAX_C) return SALUN_EINVAL;
+  if (B > (int64_t(1) << 60) / (static_cast<int64_t>(H) * W * C)) return SALUN_EINVAL;
+  if (top < 0 || left < 0 || OH < 1 || OW < 1 || OH > H || OW > W || top > H - OH || left > W - OW) return SALUN_EINVAL;
+  if (!src || !table || !dst || !salun_aligned4(table) || !salun_aligned4(dst)) return SALUN_EINVAL;
+  const int64_t pixels = B * OH * OW;
+  hipLaunchKernelGGL(k_u8_crop_to_chw_norm, dim3(salun_grid_for(pixels, SALUN_BLOCK)), dim3(SALUN_BLOCK), 0,
+                     salun_hip_stream(stream), src, table, dst, pixels, H, W, C, top, left, OH, OW);
+  SALUN_LAUNCH_CHECK();
+  return SALUN_OK;
+}

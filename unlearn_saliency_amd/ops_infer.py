@@ -1,6 +1,7 @@
-"""Tensor-level wrappers of K27 and the kernels around it (csrc/salun_conv_infer.hip, salun_pool.hip,
-salun_imgnorm.hip, salun_cls_head.hip; include/salun.h): the forward-only convolution with a folded-BatchNorm epilogue,
-the 3 x 3 / stride-2 max-pool, uint8 HWC -> normalised fp32 CHW, and the evaluation head.
+"""Tensor-level wrappers of K27, K30 and the kernels around them (csrc/salun_conv_infer.hip, salun_conv1x1_infer.hip,
+salun_pool.hip, salun_imgnorm.hip, salun_cls_head.hip, salun_row_topk.hip; include/salun.h): the forward-only
+convolutions with a folded-BatchNorm epilogue, the 3 x 3 / stride-2 max-pool, uint8 HWC -> normalised fp32 CHW (whole or
+a window), the evaluation head and the row top-k.
 
 Same conventions as ops.py: device tensors only, raw pointers and the current stream handed to libsalun.so, a failing
 call raises `SalunError`.  Every function takes an optional `out` so that a caller with its own activation buffers
@@ -98,6 +99,76 @@ def conv2d_infer_up2(x: torch.Tensor, w: torch.Tensor, scale: Optional[torch.Ten
                                             N, C, H, W, K, R, stride, pad, P, Q, int(bool(relu)), tile, _stream()),
           "salun_conv2d_infer_up2")
     return out.view(N, K, P, Q)
+
+
+def conv1x1_infer_route(N, C, HW, K, tile: int = _lib.SALUN_INFER_TILE_AUTO, aligned16: bool = True,
+                        w_aligned16: bool = True) -> Optional[str]:
+    """The label of the plan a K30 call would run, or None where K30 refuses the shape.  Host arithmetic only.
+    `aligned16`: x and y are 16-byte aligned; `w_aligned16`: w is."""
+    buf = ctypes.create_string_buffer(96)
+    rc = _lib.lib().salun_conv1x1_infer_route(N, C, c_int64(HW), K, tile, int(bool(aligned16)), int(bool(w_aligned16)),
+                                              buf, 96)
+    if rc == _lib.SALUN_EINVAL:
+        return None
+    check(rc, "salun_conv1x1_infer_route")
+    return buf.value.decode()
+
+
+def conv1x1_infer(x: torch.Tensor, w: torch.Tensor, scale: Optional[torch.Tensor] = None,
+                  shift: Optional[torch.Tensor] = None, addend: Optional[torch.Tensor] = None, relu: bool = False,
+                  out: Optional[torch.Tensor] = None, tile: int = _lib.SALUN_INFER_TILE_AUTO) -> torch.Tensor:
+    """K30: act(conv1x1(x, w) * scale[k] + shift[k] + addend): x [N, C, H, W], w [K, C] or [K, C, 1, 1] ->
+    [N, K, H, W].  One launch; the bits of conv2d_infer with R = 1."""
+    N, C, H, W = (int(v) for v in x.shape)
+    K = int(w.shape[0])
+    if w.numel() != K * C:
+        raise ValueError(f"conv1x1_infer: weight {tuple(w.shape)} does not fit x {tuple(x.shape)}")
+    if out is None:
+        out = torch.empty((N, K, H, W), dtype=torch.float32, device=x.device)
+    elif out.numel() != N * K * H * W:
+        raise ValueError("conv1x1_infer: out has the wrong size")
+    if addend is not None and addend.numel() != out.numel():
+        raise ValueError("conv1x1_infer: addend has the wrong size")
+    check(_lib.lib().salun_conv1x1_infer(_dev(x, torch.float32, "x"), _dev(w, torch.float32, "w"),
+                                         _dev(scale, torch.float32, "scale", True),
+                                         _dev(shift, torch.float32, "shift", True),
+                                         _dev(addend, torch.float32, "addend", True), _dev(out, torch.float32, "out"),
+                                         N, C, c_int64(H * W), K, int(bool(relu)), tile, _stream()),
+          "salun_conv1x1_infer")
+    return out.view(N, K, H, W)
+
+
+def u8_crop_to_chw_norm(src: torch.Tensor, table: torch.Tensor, top: int, left: int, OH: int, OW: int,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Normalize(ToTensor(src[:, top:top+OH, left:left+OW])) of uint8 [B, H, W, C] -> fp32 [B, C, OH, OW]; the crop is
+    never copied."""
+    B, H, W, C = (int(v) for v in src.shape)
+    if tuple(table.shape) != (C, 256):
+        raise ValueError(f"u8_crop_to_chw_norm: table {tuple(table.shape)} must be ({C}, 256)")
+    if out is None:
+        out = torch.empty((B, C, max(OH, 0), max(OW, 0)), dtype=torch.float32, device=src.device)
+    elif out.numel() != B * C * OH * OW:
+        raise ValueError("u8_crop_to_chw_norm: out has the wrong size")
+    check(_lib.lib().salun_u8_crop_to_chw_norm(_dev(src, torch.uint8, "src"), _dev(table, torch.float32, "table"),
+                                               _dev(out, torch.float32, "out"), c_int64(B), H, W, C, int(top), int(left),
+                                               int(OH), int(OW), _stream()), "salun_u8_crop_to_chw_norm")
+    return out.view(B, C, OH, OW)
+
+
+def row_topk(p: torch.Tensor, k: int, values: Optional[torch.Tensor] = None, indices: Optional[torch.Tensor] = None):
+    """p [B, K] fp32 -> (values [B, k] fp32, indices [B, k] int64), sorted: larger first, NaN above every number, equal
+    values by ascending index (include/salun.h)."""
+    B, K = (int(v) for v in p.shape)
+    if values is None:
+        values = torch.empty((B, k), dtype=torch.float32, device=p.device)
+    if indices is None:
+        indices = torch.empty((B, k), dtype=torch.int64, device=p.device)
+    if values.numel() != B * k or indices.numel() != B * k:
+        raise ValueError("row_topk: values / indices have the wrong size")
+    check(_lib.lib().salun_row_topk(_dev(p, torch.float32, "p"), _dev(values, torch.float32, "values"),
+                                    _dev(indices, torch.int64, "indices"), c_int64(B), K, int(k), _stream()),
+          "salun_row_topk")
+    return values.view(B, k), indices.view(B, k)
 
 
 def decoded_to_u8(x: torch.Tensor, C: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -2,7 +2,8 @@
 test_conv_bf16_exact_gpu.py): every tensor of a call lies 16-byte aligned in ONE flat allocation with GUARD floats of NaN
 before and after every input and of a sentinel pattern around every output (and in the output itself before the call);
 after the call everything but the outputs must hold the bits it was given.  A part is fp32 (4-byte words) or, with
-dtype="bf16", bf16 (two elements per word, an even number of them); guards, alignment and skew are in words either way."""
+dtype="bf16", bf16 (two elements per word; an OUTPUT without initial data may hold an odd number of them: the upper half of
+its last word is guard, checked like one); guards, alignment and skew are in words either way."""
 from ctypes import c_void_p
 
 import torch
@@ -23,7 +24,7 @@ class Arena:
     """The tensors of one call inside one flat device allocation, each behind and before GUARD floats."""
 
     def __init__(self):
-        self.parts, self.fills, self.n, self.bf16 = {}, [], 0, set()
+        self.parts, self.fills, self.n, self.bf16, self.odd = {}, [], 0, set(), {}
 
     def put(self, name, data=None, shape=None, out=False, skew=0, dtype="f32"):
         """An input (data given), an output (shape given; filled with the sentinel) or an in-place output (both).
@@ -34,8 +35,10 @@ class Arena:
             numel *= s
         assert dtype in ("f32", "bf16")
         if dtype == "bf16":
-            assert numel % 2 == 0, "a bf16 part holds whole words"
-            numel //= 2
+            if numel % 2:
+                assert out and data is None, "only an output filled with the sentinel may end inside a word"
+                self.odd[name] = numel
+            numel = (numel + 1) // 2
             self.bf16.add(name)
             data = None if data is None else _bf16_words(data)
         start = self.n + GUARD + skew
@@ -67,11 +70,16 @@ class Arena:
             if out:                                # everything between two outputs: inputs and all the guards
                 assert torch.equal(after[lo:start], self.host[lo:start]), "a guard or an input was written"
                 lo = start + numel
+        for name in self.odd:                      # the half word behind an odd-sized bf16 output
+            last = self.parts[name][0] + self.parts[name][1] - 1
+            assert after[last:last + 1].view(torch.int16)[1] == self.host[last:last + 1].view(torch.int16)[1], "a guard was written"
         return after
 
     def part(self, after, name):
         """The output `name` of a downloaded arena."""
         start, numel, shape, _ = self.parts[name]
+        if name in self.odd:
+            return after[start:start + numel].view(torch.int16)[:self.odd[name]].view(shape)
         if name in self.bf16:                      # bf16 bits
             return after[start:start + numel].view(torch.int16).view(shape)
         return after[start:start + numel].view(torch.float32).view(shape)

@@ -8,6 +8,7 @@ import itertools
 import pytest
 
 import bf16_routes as M
+import gemm_bf16_ref_cpu as GB
 import test_conv_bf16_gpu as TC
 import test_gemm_bf16_gpu as TG
 
@@ -44,6 +45,9 @@ NT_CASES = list(_params(TG.test_gemm_bf16_nt_matches_fp32_matmul_of_the_rounded_
     [(4096, 640, 320), (4096, 320, 320), (128, 96, 64), (128, 64, 40)]   # test_variants_agree_bitwise_and_shapes_outside_...
 TN_CASES = list(_params(TG.test_gemm_bf16_tn_weight_gradient_matches_fp32_matmul_of_the_rounded_operands)[0].args[1]) + \
     [(512, 640, 320), (64, 48, 32)]
+# the shapes of the exact-answer tests of K16 (gemm_bf16_ref_cpu.py), refusals included
+NT_CASES = list(dict.fromkeys(NT_CASES + [(c.M, c.N, c.K) for c in GB.NT_CASES] + [r[:3] for r in GB.NT_REFUSED] + GB.AGREE))
+TN_CASES = list(dict.fromkeys(TN_CASES + [(c.M, c.Na, c.Nb) for c in GB.TN_CASES] + [r[:3] for r in GB.TN_REFUSED]))
 
 CHANNELS = [32, 64, 96, 160, 256, 320, 640, 1280, 2560]
 FILTERS = [(1, 1, 0), (1, 2, 0), (3, 1, 1), (3, 2, 1), (3, 1, 0), (3, 1, 2)]
